@@ -14,13 +14,18 @@ With N > 1 GPUs every rank encodes its own stream(s): independent streams, no da
 RCCL is used outside the timed region only: one broadcast of the table blob, one gather of the MP3 bytes to rank 0
 (north_star: "a single RCCL broadcast/gather ... for input/output buffers only").
 
-Every stream's FULL output is compared (md5 + length) with tests/golden/full_md5.json, produced from the unmodified
-reference by tests/tools/gen_full_md5.sh; a prefix is additionally byte-compared with the CPU oracle.
+A plain run sets up, warms up, times exactly --steps steps and prints ONE JSON line (rank 0) with the contract fields for the
+chosen config and the md5 of what the last step encoded.  --dump-outputs DIR also writes that step's MP3 bytes as .npy files
+(see dump_outputs), so that two builds can be compared output for output.
 
-Prints ONE JSON line (rank 0): the contract fields for the chosen config, `roofline` (dominant kernel: algorithmic bytes /
-measured kernel time vs HBM peak, PMC traffic), `roofline_compute` (the same kernel against the VALU issue ceiling of its
-measured instruction mix), `cpu_baseline` (the plain-C oracle on a bounded sample, one host core; plus the Node reference's
-figures measured where /root/reference exists) and, at N = 1, `other_configs`: configs 2, 4, 5 and the `bursts` material.
+--full adds everything else, each part measured or checked after the timed steps (the Node lines before the GPU is opened):
+every stream's FULL output compared (md5 + length) with tests/golden/full_md5.json, produced from the unmodified reference by
+tests/tools/gen_full_md5.sh, and a prefix byte-compared with the CPU oracle; at N > 1 the RCCL gather of the MP3 bytes to
+rank 0, re-hashed there; `kernels_ms` (one extra step with HIP events per kernel), `roofline` (dominant kernel: algorithmic
+bytes / measured kernel time vs HBM peak, PMC traffic), `roofline_compute` (the same kernel against the VALU issue ceiling of
+its measured instruction mix), `cpu_baseline` (the plain-C oracle on a bounded sample, one host core; plus the Node
+reference's figures measured where its single-file build is in oracle/_ref/) and, at N = 1, `other_configs`: the other
+configs and materials, the host-buffer call and the Node drop-in lines.
 """
 import argparse
 import ctypes
@@ -63,7 +68,7 @@ def run_frame_range_shards(args, lib, dist, torch, np, dev, dev_ord, world, rank
     ranges that the ranks encode side by side (second mode; strong scaling).  The encoder state at a cut is speculated
     (lhip_seek + H warm-up frames), verified (the state blob after the warm-up must equal the blob of the rank that encoded up to
     the cut) and, on a miss, transplanted from that rank and the range encoded again -- so the concatenation is always byte for
-    byte what one stream produces; it is checked against the reference's md5 of the whole stream."""
+    byte what one stream produces; --full checks it against the reference's md5 of the whole stream."""
     import lamejs_amd
     import pcm
     ch, kbps, corpus, seed, H = 2, 128, args.shard_corpus, 12345, args.shard_warmup
@@ -196,16 +201,20 @@ def run_frame_range_shards(args, lib, dist, torch, np, dev, dev_ord, world, rank
         allstats = [None] * world
         dist.all_gather_object(allstats, stats)
     if rank == 0:
-        ent = table.get((corpus, ch, kbps, nfr, seed, False, False))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [whole], (nfr + 4) * (144000 * kbps // SR + 1))
         md5 = hashlib.md5(whole).hexdigest()
         line = {"metric": f"1152-sample frames/s encoded (44.1kHz {kbps}kbps CBR); bit-exact", "value": round((nfr - 1) * args.steps / dt, 1), "unit": "frames/s",
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000.0 * dt / args.steps, 3), "higher_is_better": True,
                 "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                 "config": {"workload": f"ONE stream (BASELINE configs[2] material: stereo 44.1kHz 128kbps CBR, {nfr} synthetic {corpus} frames) cut into {world} frame range(s), "
                                        f"{H} warm-up frames per cut, state verified at every cut",
-                           "bit_exact_full": (None if ent is None else bool(ent[0] == md5 and ent[1] == len(whole))), "output_md5": md5,
+                           "output_md5": md5,
                            "cut_state_mismatches": sum(s_["state_mismatches"] for s_ in allstats) // max(world, 1),
                            "ranges_encoded_again": sum(s_["ranges_encoded_again"] for s_ in allstats)}}
+        if args.full:
+            ent = table.get((corpus, ch, kbps, nfr, seed, False, False))
+            line["config"]["bit_exact_full"] = None if ent is None else bool(ent[0] == md5 and ent[1] == len(whole))
         _print_line(line)
 
 
@@ -218,6 +227,33 @@ def _print_line(line):
         pass
     sys.stdout.write(json.dumps(line) + "\n")
     sys.stdout.flush()
+
+
+DUMP_MAX_VALUES = 12 << 20      # float32 values of the byte sample over ALL ranks: 48 MiB, inside the 64 MB a whole dump may take
+
+
+def dump_outputs(dirpath, outs, cap, suffix="", max_values=DUMP_MAX_VALUES):
+    """--dump-outputs: what the timed path hands its caller in the last step -- every stream's MP3 bytes -- as float32 .npy files.
+    The streams lie end to end, each in a slot of `cap` bytes (the output capacity, fixed by the arguments), so that a position means the
+    same in every build; a slot's bytes past what its stream wrote read -1.  Above `max_values` positions (a rank's share of
+    DUMP_MAX_VALUES) a fixed, seeded sample of them is kept.  mp3_nbytes: the bytes every stream wrote."""
+    import numpy as np
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    total = cap * len(outs)
+    if total <= max_values:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(1152).choice(total, max_values, replace=False))
+    vals = np.full(len(pos), -1.0, dtype=np.float32)
+    bounds = np.searchsorted(pos, np.arange(len(outs) + 1, dtype=np.int64) * cap)
+    for i, o in enumerate(outs):
+        off = pos[bounds[i]:bounds[i + 1]] - i * cap
+        b = np.frombuffer(o, dtype=np.uint8)
+        m = off < len(b)
+        vals[bounds[i]:bounds[i + 1]][m] = b[off[m]]
+    np.save(d / f"mp3_bytes{suffix}.npy", vals)
+    np.save(d / f"mp3_nbytes{suffix}.npy", np.array([len(o) for o in outs], dtype=np.float64))
 
 
 def alg_bytes_per_frame(ch, kbps):
@@ -340,7 +376,12 @@ def main():
     ap.add_argument("--no-cpu-aggregate", action="store_true", help="skip the all-cores leg of the CPU baseline")
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL gather of the MP3 bytes to rank 0 (N > 1)")
     ap.add_argument("--no-pipeline", action="store_true", help="(accepted for older scripts: there is only one batch in flight since round 4 -- two were measured slower and removed)")
+    ap.add_argument("--full", action="store_true", help="also the checks against the reference and the oracle, per-kernel times and rooflines, the CPU baselines and "
+                                                        "(N = 1) the other configs and drop-in lines; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the MP3 bytes of the last timed step to DIR/*.npy (float32, one file per rank; a fixed, seeded sample above 12 Mi bytes over all ranks)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` started plainly (no launcher, no WORLD_SIZE in the environment) launches its own N ranks: the same
     # command line under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` on 127.0.0.1, one rank per GPU.  Under a
@@ -358,7 +399,7 @@ def main():
             table[(e["corpus"], e["channels"], e["kbps"], e["frames"], e["seed"], bool(e.get("joint")), bool(e.get("reservoir")))] = (e["md5"], e["bytes"])
     sim = os.environ.get("LAMEJS_BENCH_HOSTSIM") == "1"       # tests only: gloo + the host simulation behind the same C ABI
     node_lines = {}
-    if args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not sim and not args.no_extras and not args.frames and not args.streams and args.config != "shard3":
+    if args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not sim and not args.no_extras and not args.frames and not args.streams and args.config != "shard3":
         node_lines = node_dropin_lines(table)
 
     import numpy as np
@@ -564,8 +605,13 @@ def main():
     wl = Workload(key)
     dt = wl.timed(args.steps, args.warmup)
     outs = wl.outputs()
-    full, prefix, md5s = wl.check(outs)
-    kern = wl.kernel_times() if not sim else {}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs, wl.out_cap, f"_rank{rank}" if world > 1 else "", DUMP_MAX_VALUES // world)
+    if args.full:
+        full, prefix, md5s = wl.check(outs)
+    else:
+        full, prefix, md5s = None, None, [hashlib.md5(o).hexdigest() for o in outs]
+    kern = wl.kernel_times() if args.full and not sim else {}
 
     # ---- N > 1: verdicts of all ranks; RCCL gather of the MP3 bytes to rank 0 (untimed), re-hashed there ----
     dom_ms = None           # this rank's dominant kernel: (name, ms per launch) -- at N > 1 the roofline is computed from the slowest rank's
@@ -579,7 +625,7 @@ def main():
         allv = [None] * world
         dist.all_gather_object(allv, verdicts[0])
         verdicts = allv
-        if not args.no_gather:
+        if args.full and not args.no_gather:
             nmax = max(max(v[4]) for v in verdicts)
             mine = torch.zeros(wl.ns * nmax, dtype=torch.uint8, device=dev)
             for i in range(wl.ns):
@@ -607,20 +653,22 @@ def main():
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": wl.describe(), "frames_per_step_per_gpu": wl.frames_per_step,
                        "input": "Int16 PCM resident in HBM", "output": "MP3 bytes in HBM",
-                       "bit_exact_full": (None if any(f is None for f in all_full) else all(all_full)),
-                       "bit_exact_full_note": "md5 + length of every stream's whole output vs tests/golden/full_md5.json (unmodified reference under node)",
-                       "bit_exact_prefix_vs_oracle": (None if any(v[3] is None for v in verdicts) else all(v[3] for v in verdicts)),
                        "seed_repaired_frames": wl.repaired, "repair_iterations": wl.repair_iters,
                        "output_md5_per_rank": [v[1][0] if len(v[1]) == 1 else hashlib.md5("".join(v[1]).encode()).hexdigest() for v in verdicts],
-                       "rccl_gather_of_outputs_rehashed_ok": gathered_ok,
                        "stream_seeds_per_rank": [[v[5][0], v[5][-1], len(v[5])] for v in verdicts],       # [first, last, count]: ranks encode disjoint streams
                        "distinct_streams": len({s_ for v in verdicts for s_ in v[5]}),
                        # which GPU every rank really sat on (a multi-GPU line validates itself: N ranks, N distinct devices)
                        "devices_per_rank": [v[6] for v in verdicts],
                        "distinct_devices": len({(v[6].get("hip_device_pci_bus_id"), v[6].get("hip_device_uuid")) for v in verdicts}),
                        "rccl_world_size": rccl_world, "collective_backend": (None if not use_dist else "gloo (host simulation)" if sim else "nccl (RCCL)")},
-            "kernels_ms": kern,
         }
+        if args.full:
+            line["config"].update({
+                "bit_exact_full": (None if any(f is None for f in all_full) else all(all_full)),
+                "bit_exact_full_note": "md5 + length of every stream's whole output vs tests/golden/full_md5.json (unmodified reference under node)",
+                "bit_exact_prefix_vs_oracle": (None if any(v[3] is None for v in verdicts) else all(v[3] for v in verdicts)),
+                "rccl_gather_of_outputs_rehashed_ok": gathered_ok})
+            line["kernels_ms"] = kern
         if world > 1 and line["config"]["distinct_devices"] != world:
             raise SystemExit(f"bench.py: {world} ranks report {line['config']['distinct_devices']} distinct devices: {line['config']['devices_per_rank']}")
         dom = max(kern, key=lambda k_: kern[k_]["ms"]) if kern else None
@@ -667,7 +715,7 @@ def main():
                                             "source": f"profiles/{pf.name} (PMC counts of this workload on the code of that measurement pass: they go stale with every kernel change) + the issue microbenchmark in it (ceiling of that mix)"}
 
     # ---- the other configurations (N = 1 only): each is its own short run, md5-checked like the main one ----
-    if world == 1 and not args.no_extras and not args.frames and not args.streams:
+    if args.full and world == 1 and not args.no_extras and not args.frames and not args.streams:
         others = {}
         for k2 in (2, 3, 4, 5, "bursts", "joint", "joint_bursts", "reservoir", "reservoir256", "reservoir512"):
             if k2 == key:
@@ -720,7 +768,7 @@ def main():
             others[nm] = e
         line["other_configs"] = others
 
-    if rank == 0 and args.cpu_seconds > 0 and world == 1:       # the CPU baseline is reported at N = 1 only
+    if args.full and rank == 0 and args.cpu_seconds > 0 and world == 1:       # the CPU baseline is reported at N = 1 only
         from oracle_py import oracle_encode
         L, R = wl.pcs[0][0], wl.pcs[0][1]
         k = min(2000, wl.nfr)

@@ -51,17 +51,19 @@ def test_two_ranks_gloo(tmp_path, ch, kbps, n_streams):
 
 
 @pytest.mark.parametrize("cfg,extra,ch,kbps", [("3", ["--frames", "7"], 2, 128), ("4", ["--frames", "5"], 2, 320), ("5", ["--streams", "3", "--frames", "5"], 1, 128)])
-def test_bench_py_two_ranks_gloo(cfg, extra, ch, kbps):
+def test_bench_py_two_ranks_gloo(tmp_path, cfg, extra, ch, kbps):
     """bench.py ITSELF with world_size 2 (its rank seeds, table broadcast, barrier-bracketed timing with the max over ranks,
     verdict gather, gather of the MP3 bytes to rank 0): gloo + the host simulation of the kernels behind the same C ABI
-    (LAMEJS_BENCH_HOSTSIM=1), a handful of frames per stream.  Every rank's stream must equal the oracle's bytes."""
+    (LAMEJS_BENCH_HOSTSIM=1), a handful of frames per stream.  Every rank's stream must equal the oracle's bytes, in the line and
+    in the rank's --dump-outputs file; the dump of the whole run stays inside its 64 MB."""
+    import numpy as np
     if not HOSTSIM.exists():
         pytest.skip("host simulation not built (python -c 'import __graft_entry__ as g; g.build()')")
     env = dict(os.environ, LAMEJS_HIP_LIB=str(HOSTSIM), LAMEJS_BENCH_HOSTSIM="1", MASTER_ADDR="127.0.0.1")
     port = 31500 + (os.getpid() % 2000) + int(cfg)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", cfg,
-                        "--cpu-seconds", "0"] + extra, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--cpu-seconds", "0", "--dump-outputs", str(tmp_path / "dump")] + extra, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["unit"] == "frames/s"
@@ -70,14 +72,43 @@ def test_bench_py_two_ranks_gloo(cfg, extra, ch, kbps):
     ns = int(extra[extra.index("--streams") + 1]) if "--streams" in extra else 1
     nfr = int(extra[extra.index("--frames") + 1])
     assert line["value"] > 0 and c["frames_per_step_per_gpu"] == ns * (nfr - 1)
+    assert sorted(f.name for f in (tmp_path / "dump").iterdir()) == ["mp3_bytes_rank0.npy", "mp3_bytes_rank1.npy", "mp3_nbytes_rank0.npy", "mp3_nbytes_rank1.npy"]
+    assert sum(f.stat().st_size for f in (tmp_path / "dump").iterdir()) <= 64_000_000
     for rank in range(2):
+        dumped = np.load(tmp_path / "dump" / f"mp3_bytes_rank{rank}.npy")
+        cap = len(dumped) // ns
         md5s = []
         for i in range(ns):
             seed = (12345 + rank) if cfg != "5" else 1000 + rank * ns + i
             L, R = pcm.sine(1152 * nfr, ch, seed=seed)
-            md5s.append(hashlib.md5(oracle_encode(ch, 44100, kbps, L, R, flush=False)).hexdigest())
+            want_i = oracle_encode(ch, 44100, kbps, L, R, flush=False)
+            assert dumped[i * cap:i * cap + len(want_i)].astype(np.uint8).tobytes() == want_i, (rank, i)
+            md5s.append(hashlib.md5(want_i).hexdigest())
         want = md5s[0] if ns == 1 else hashlib.md5("".join(md5s).encode()).hexdigest()
         assert c["output_md5_per_rank"][rank] == want, (rank, c)
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """dump_outputs directly: within its budget every slot position (bytes the stream did not write read -1); above it the fixed sample
+    of positions seeded with 1152, the same in every call, each kept value the byte at its own stream and offset (the bytes here are
+    their own positions).  bench.py gives every rank DUMP_MAX_VALUES // world of a 48 MiB budget."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    assert bench.DUMP_MAX_VALUES * 4 <= 64_000_000 - 2 ** 20
+    cap, lens = 80, (80, 61, 5)
+    outs = [bytes(i * cap + j for j in range(n)) for i, n in enumerate(lens)]
+    expect = np.array([p if p % cap < lens[p // cap] else -1 for p in range(cap * len(lens))], dtype=np.float32)
+    bench.dump_outputs(tmp_path / "whole", outs, cap, max_values=1000)
+    assert np.array_equal(np.load(tmp_path / "whole" / "mp3_bytes.npy"), expect)
+    assert np.array_equal(np.load(tmp_path / "whole" / "mp3_nbytes.npy"), np.array(lens, dtype=np.float64))
+    pos = np.sort(np.random.default_rng(1152).choice(cap * len(lens), 100, replace=False))
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, outs, cap, "_rank1", max_values=100)
+        got = np.load(tmp_path / run / "mp3_bytes_rank1.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, expect[pos]), run
+    assert {int(v) // cap for v in got if v >= 0} == {0, 1, 2}
 
 
 @pytest.mark.parametrize("world,corpus,nfr", [(2, "sine", 30), (3, "bursts", 90)])
@@ -125,7 +156,7 @@ def test_bench_py_plain_launch_spawns_its_ranks(cfg, extra, ch, kbps):
         pytest.skip("host simulation not built (python -c 'import __graft_entry__ as g; g.build()')")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LAMEJS_HIP_LIB=str(HOSTSIM), LAMEJS_BENCH_HOSTSIM="1")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", cfg, "--cpu-seconds", "0"] + extra,
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", cfg, "--full", "--cpu-seconds", "0"] + extra,
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -147,6 +178,39 @@ def test_bench_py_plain_launch_frame_range_shards():
     assert line["n_gpus"] == 2 and line["config"]["output_md5"] == hashlib.md5(oracle_encode(2, 44100, 128, L, R, flush=False)).hexdigest()
 
 
+def test_bench_py_plain_run_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the contract fields only; --dump-outputs writes what the last step
+    encoded -- every stream's bytes, float32 -- the same in two runs with the same arguments, and the oracle's bytes for every stream."""
+    import numpy as np
+    if not HOSTSIM.exists():
+        pytest.skip("host simulation not built (python -c 'import __graft_entry__ as g; g.build()')")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(LAMEJS_HIP_LIB=str(HOSTSIM), LAMEJS_BENCH_HOSTSIM="1")
+    ns, nfr = 2, 4
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "5", "--streams", str(ns), "--frames", str(nfr),
+                            "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert not {"kernels_ms", "roofline", "cpu_baseline", "other_configs"} & set(line) and "bit_exact_prefix_vs_oracle" not in line["config"]
+    got = np.load(tmp_path / "a" / "mp3_bytes.npy")
+    nbytes = np.load(tmp_path / "a" / "mp3_nbytes.npy")
+    assert got.dtype == np.float32 and nbytes.dtype == np.float64 and len(nbytes) == ns
+    assert np.array_equal(got, np.load(tmp_path / "b" / "mp3_bytes.npy")) and np.array_equal(nbytes, np.load(tmp_path / "b" / "mp3_nbytes.npy"))
+    cap = len(got) // ns
+    md5s = []
+    for i in range(ns):
+        L, R = pcm.sine(1152 * nfr, 1, seed=1000 + i)
+        want = oracle_encode(1, 44100, 128, L, R, flush=False)
+        slot = got[i * cap:(i + 1) * cap]
+        assert int(nbytes[i]) == len(want) and slot[:len(want)].astype(np.uint8).tobytes() == want and (slot[len(want):] == -1).all(), i
+        md5s.append(hashlib.md5(want).hexdigest())
+    assert line["config"]["output_md5_per_rank"] == [hashlib.md5("".join(md5s).encode()).hexdigest()]
+
+
 def test_bench_py_refuses_a_launcher_with_another_world_size():
     """Under a launcher bench.py does not re-launch; a WORLD_SIZE that disagrees with --gpus is an error message, not an assertion trace."""
     env = dict(os.environ, WORLD_SIZE="1", LAMEJS_BENCH_HOSTSIM="1", LAMEJS_HIP_LIB=str(HOSTSIM), LAMEJS_BENCH_NO_DIST="1")
@@ -166,7 +230,7 @@ def test_bench_py_plain_launch_world8(cfg, extra, ch, kbps):
         pytest.skip("host simulation not built (python -c 'import __graft_entry__ as g; g.build()')")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LAMEJS_HIP_LIB=str(HOSTSIM), LAMEJS_BENCH_HOSTSIM="1", OMP_NUM_THREADS="1")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--config", cfg, "--cpu-seconds", "0", "--check-frames", "3"] + extra,
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--config", cfg, "--full", "--cpu-seconds", "0", "--check-frames", "3"] + extra,
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -2,16 +2,31 @@
  * TEST TOOL: compare every table/scalar built by lamejs_amd/js/tables.js with the value
  * held by a live reference encoder instance (where the reference exposes it).
  * usage: node tests/tools/check_tables_vs_ref.js   -> prints "OK n checks" or the mismatches, exit code 0/1
+ *        node tests/tools/check_tables_vs_ref.js --record tests/golden/ref_tables.json     (also writes the reference's values, as digests)
+ *        node tests/tools/check_tables_vs_ref.js --recorded tests/golden/ref_tables.json   (no reference needed: tables.js against that file)
  */
 'use strict';
-const { refEncoder } = require('./ref_harness.js');
+const fs = require('fs');
+const crypto = require('crypto');
 const tables = require('../../lamejs_amd/js/tables.js');
+
+const RECORD = process.argv[2] === '--record' ? process.argv[3] : null;
+const RECORDED = process.argv[2] === '--recorded' ? process.argv[3] : null;
+/* without a reference the reference's side is a stand-in that takes any property access or call; the comparisons then collect tables.js's values */
+const standIn = new Proxy(function () {}, { get: (t, k) => (k === Symbol.toPrimitive ? () => 0 : standIn), apply: () => standIn });
+const refEncoder = RECORDED ? () => standIn : require('./ref_harness.js').refEncoder;
+const collected = {};
+/* one string per value that same() tells apart: +0 and -0 alike, NaN equal to itself */
+const collect = (name, v) => { (collected[name] = collected[name] || []).push(v === 0 ? '0' : String(v)); };
+const digest = (vals) => crypto.createHash('md5').update(vals.join(',')).digest('hex').slice(0, 16);
 
 let nchk = 0, bad = 0;
 function same(a, b) { return Object.is(a, b) || (a === b); }
 function cmp(name, mine, ref, n) {
     n = n === undefined ? mine.length : n;
     for (let i = 0; i < n; i++) {
+        if (RECORDED) { collect(name, mine[i]); continue; }
+        if (RECORD) collect(name, ref[i]);
         nchk++;
         if (!same(mine[i], ref[i])) {
             if (bad < 40) console.log('MISMATCH', name, i, mine[i], ref[i]);
@@ -116,6 +131,21 @@ for (const [ch, sr, kb, joint] of configs) {
     cmpS(tag + 'OldValue', 180, gfc.OldValue[0]);
     cmpS(tag + 'CurrentStep', 4, gfc.CurrentStep[0]);
     cmpS(tag + 'slot_lag', p.frac_SpF, gfc.slot_lag);
+}
+if (RECORD) {
+    const lines = Object.keys(collected).map((k) => `  ${JSON.stringify(k)}: [${collected[k].length}, "${digest(collected[k])}"]`);
+    fs.writeFileSync(RECORD, `{"generator": "node tests/tools/check_tables_vs_ref.js --record", "values": {\n${lines.join(',\n')}\n}}\n`);
+}
+if (RECORDED) {
+    const want = JSON.parse(fs.readFileSync(RECORDED, 'utf8')).values;
+    for (const k of new Set(Object.keys(want).concat(Object.keys(collected)))) {
+        const got = collected[k] ? [collected[k].length, digest(collected[k])] : null;
+        nchk += got ? got[0] : 1;
+        if (!got || !want[k] || got[0] !== want[k][0] || got[1] !== want[k][1]) {
+            if (bad < 40) console.log('MISMATCH', k, 'tables.js', got, 'reference', want[k]);
+            bad++;
+        }
+    }
 }
 if (bad) { console.log('FAILED:', bad, 'mismatches of', nchk); process.exit(1); }
 console.log('OK', nchk, 'checks');

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06m; mkdir -p $O
 cd $R
 timeout 60 tools/_build/ubench_issue $O/ubench_issue.json > $O/ubench_issue.txt 2>&1; tail -3 $O/ubench_issue.txt
 cd /tmp && export TMPDIR=/tmp
-B3="python $R/bench.py --cpu-seconds 0 --steps 1 --warmup 1 --check-frames 0 --no-extras"
+B3="python $R/bench.py --full --cpu-seconds 0 --steps 1 --warmup 1 --check-frames 0 --no-extras"
 B2="$B3 --config 2"
 for c in 3 2; do
   eval B=\$B$c

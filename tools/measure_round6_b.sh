@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06m; mkdir -p $O
 cd $R
 timeout 400 python -m pytest tests -m gpu -q --timeout 200 > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.err
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.err
 python - <<'PY'
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r06m/bench_default.json').read().strip().splitlines()[-1])
@@ -11,7 +11,7 @@ print('value', d['value'], 'ms', d['ms_per_step'], 'bit_exact_full', d['config']
 for k,v in d.get('other_configs',{}).items(): print(k, {a:b for a,b in v.items() if a in ('value','frames_per_s','ms_per_step','ms_per_call','bit_exact_full','vs_device_resident','vs_c_abi_host_call','call_us_median','error')})
 print(d['kernels_ms']); print(d.get('roofline')); print(json.dumps(d.get('cpu_baseline'))[:900])
 PY
-LAMEJS_BENCH_FORCE_DIST=1 timeout 200 python bench.py --config 3 --no-extras --cpu-seconds 0 --steps 2 > $O/bench_nccl_world1_config3.json 2> $O/bench_nccl_world1_config3.err; tail -c 200 $O/bench_nccl_world1_config3.err
+LAMEJS_BENCH_FORCE_DIST=1 timeout 200 python bench.py --full --config 3 --no-extras --cpu-seconds 0 --steps 2 > $O/bench_nccl_world1_config3.json 2> $O/bench_nccl_world1_config3.err; tail -c 200 $O/bench_nccl_world1_config3.err
 {
 echo "GPU fuzz on the final code of round 6 (tests/tools/fuzz_gpu.py <n> <seed> <family>: random material, random chunking, GPU output vs the CPU oracle)"
 for spec in "3000 650001 mpeg1" "1600 650002 lsf" "800 650003 resample" "400 650004 lowrate" "1200 650005 mpeg1 joint" "510 650006 mpeg1 reservoir" "400 650007 mpeg1 stereo whole" "300 650008 lsf joint reservoir"; do

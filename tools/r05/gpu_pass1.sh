@@ -11,7 +11,7 @@ for ch in 2 1; do
 done
 LAMEJS_HIP_NO_FRAME_KERNEL=1 timeout 120 node tests/tools/bench_dropin.js calls 2 128 sine 600 1 | cut -c1-600 > $O/calls_ch2_separate_kernels.json; cat $O/calls_ch2_separate_kernels.json
 timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -x -k "live_reference or fixture_md5s" > $O/pytest_live_reference.txt 2>&1; tail -5 $O/pytest_live_reference.txt
-timeout 900 python bench.py --steps 5 --warmup 1 > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.err
+timeout 900 python bench.py --full --steps 5 --warmup 1 > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.err
 python - <<'PY'
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r05_pass1/bench.json').read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ LAMEJS_HIP_LIB=$R/lamejs_amd/lib/variants/nopipe.so calls no_count_helper
 LAMEJS_HIP_NO_SMALL_CALLS=1 calls no_small_call_path
 } 2>&1 | tee $O/calls_ab.txt
 timeout 900 python -m pytest tests -m gpu -q -x --durations=5 > $O/pytest_gpu.txt 2>&1; tail -12 $O/pytest_gpu.txt
-timeout 900 python bench.py --steps 5 --warmup 1 > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+timeout 900 python bench.py --full --steps 5 --warmup 1 > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
 python - <<'PY'
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r05_pass2/bench.json').read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05_pass5; mkdir -p $O
 cd $R
 for c in reservoir reservoir256 reservoir512; do
-  timeout 200 python bench.py --no-extras --cpu-seconds 0 --steps 4 --warmup 1 --check-frames 0 --config $c 2>/dev/null | python -c "
+  timeout 200 python bench.py --full --no-extras --cpu-seconds 0 --steps 4 --warmup 1 --check-frames 0 --config $c 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('config $c', 'ms_per_step', d['ms_per_step'], 'frames/s', d['value'], 'bit_exact_full', d['config']['bit_exact_full'])"
 done 2>&1 | tee $O/configs.txt

@@ -6,7 +6,7 @@ for spec in "300 680001 mpeg1 framecalls" "150 680002 lsf framecalls" "100 68000
 done
 } | tee $O/fuzz.txt
 bash tools/r05/gpu_ab_calls.sh 2>&1 | tee $O/calls_ab.txt
-B="python bench.py --no-extras --cpu-seconds 0 --steps 3 --warmup 1 --check-frames 0"
+B="python bench.py --full --no-extras --cpu-seconds 0 --steps 3 --warmup 1 --check-frames 0"
 {
 for rep in 1 2; do for lib in lamejs_amd/lib/liblamejs_hip.so lamejs_amd/lib/variants/nobsahead.so; do for c in reservoir reservoir256; do
   LAMEJS_HIP_LIB=$R/$lib timeout 200 $B --config $c 2>/dev/null | python -c "

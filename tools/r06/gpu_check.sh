@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06_check; mkdir -p $O
 cd $R
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 timeout 900 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -c 200 $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -c 200 $O/bench.err
 python - <<'PY'
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r06_check/bench.json').read().strip().splitlines()[-1])
