@@ -66,7 +66,8 @@ def test_set_devices_argument_handling():
 def test_device_code_resources(tmp_path):
     """The resource usage the design rests on, read from the shipped library's own gfx950 code object (no GPU needed): the persistent
     quantization kernel spills nothing to scratch memory, stays within 128 registers (4 waves per SIMD) and two of its workgroups fit the
-    160 KB of LDS of a CU; the batch kernels of the steady-state path use no scratch either."""
+    160 KB of LDS of a CU; the batch kernels of the steady-state path use no scratch either; the one-frame and the
+    per-stream reservoir kernel run two waves per SIMD, fit a CU's LDS, and the one-frame kernel stays far below the scratch size that slows its launch (4.6)."""
     import shutil
     import subprocess
     llvm = "/opt/rocm/lib/llvm/bin"
@@ -92,3 +93,13 @@ def test_device_code_resources(tmp_path):
         ks = [v for k, v in kern.items() if re.match(rf"_Z\d+{name}(I|N|5|E)", k)]
         assert ks, name
         assert all(v["private_segment_fixed_size"] == 0 for v in ks), (name, ks)
+    # the latency kernels: eight waves per workgroup on four SIMDs (g_resv_stream: two workgroups of four) are two waves per SIMD -- 256 registers; a
+    # workgroup's LDS must fit a CU; past ~0.5 KB of scratch per lane a one-frame launch itself gets slower (the comment above g_frame's stage loop)
+    fr = {k: v for k, v in kern.items() if k.startswith("_Z7g_frameILi0") or k.startswith("_Z7g_frameILi1")}
+    assert len(fr) == 2, sorted(kern)
+    rs = {k: v for k, v in kern.items() if k.startswith("_Z13g_resv_stream")}
+    assert len(rs) == 1, sorted(kern)
+    for k, v in {**fr, **rs}.items():
+        assert v["vgpr_count"] <= 256 and v["group_segment_fixed_size"] <= 160 * 1024, (k, v)
+    for k, v in fr.items():
+        assert v["private_segment_fixed_size"] < 512, (k, v)
