@@ -25,6 +25,17 @@
  * stream then depend on each other (budget and masking), so the library encodes one frame per stream per launch -- batches of many
  * streams are what uses the GPU -- the byte count of a call is data-dependent, and every call synchronises (sync = 0 is ignored).
  *
+ * Resampling by a non-integer ratio.  By default a configuration whose output rate is not an integer fraction of the input rate is refused
+ * (the reference feeds itself NaN samples there once a call is long enough).  A blob built with { fractionalResample: true } carries the
+ * reference's set-up for it (filter_l = 31, all 2 * bpc + 1 windows); the stream is then a CALL-SEQUENCE stream: the bytes of every
+ * lhip_encode are the reference's for the same sequence of call lengths (they do depend on where the calls are cut -- the reference's do).
+ * A call the reference would not consume whole returns -4 and consumes nothing, lhip_last_error() names the length that is always accepted
+ * (lhip_frac_call_limit(): 1585 samples for 44100 -> 32000 Hz, never less than 576); each call completes 0 or 1 frame; lhip_encode_output_bytes
+ * stays exact (-4 for a call that would be refused).  lhip_flush: the flush frames whose input the reference still computes from whole
+ * positions are encoded byte for byte; those in which it encodes its own NaN samples (audibly empty there too) are replaced by silent frames
+ * of equal length and header; the stream ends with its flush (a later lhip_encode returns -4).  lhip_seek, lhip_state_get and lhip_state_set
+ * return -4 for such streams; the bit reservoir cannot be combined with it.  lhip_encode_batch over such streams may mix configurations.
+ *
  * Semantics preserved: any chunking of the same sample stream yields the same bytes; a call
  * returns the bytes of all whole frames completed by that call (possibly 0); errors are negative
  * return codes mirroring the reference (-1 output buffer too small, -3 bad handle, -4 internal/device
@@ -179,6 +190,16 @@ int lhip_debug_set_spec_seed(int start, int step);
  * two contexts at once) run against real HIP on a box with one GPU.  lhip_debug_release_context(d) gives back the stream the library created for such a
  * context (and the side stream of its ATH scan) once no stream lives on it; returns 0 or <0. */
 int lhip_debug_release_context(int device);
+
+/* Non-integer-ratio streams (blob built with { fractionalResample: true }): the call length that is accepted whatever calls came before
+ * (0 for every other stream: any length goes); < 0: bad handle. */
+int64_t lhip_frac_call_limit(const lhip_stream* s);
+/* Test hooks for such streams -- the host arithmetic alone, nothing is encoded or consumed.  lhip_debug_frac_call: the output-rate samples (*k)
+ * and frames (*frames: 0, 1, or -1 with return code -4 for a call that would be refused) the next lhip_encode of nsamples would make.
+ * lhip_debug_frac_flush: what lhip_flush would emit now: returns the number of frames, fills bytes[i] and clean[i] (1: encoded from finite
+ * samples, byte-exact; 0: a silent stand-in for a frame the reference makes of NaN samples) for the first `cap` of them. */
+int lhip_debug_frac_call(const lhip_stream* s, size_t nsamples, int32_t* k, int32_t* frames);
+int lhip_debug_frac_flush(const lhip_stream* s, int32_t* bytes, int32_t* clean, int cap);
 
 const char* lhip_last_error(void);
 const char* lhip_version(void);

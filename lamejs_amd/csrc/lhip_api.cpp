@@ -161,6 +161,33 @@ LHIP_DEV void kb_resample_elem(const Tables& T, float* dst, const int16_t* src, 
     dst[t] = (float)xvalue;
 }
 
+// fill_buffer_resample (Lame.js:1769-1800) for a NON-integer ratio (extension { fractionalResample }: Tables::rs_frac).  There filter_l = 31,
+// BLACKSIZE = 32 and filter_l / 2 = 15.5: output k of a call sits at input time k * ratio - itime (itime: the resampler's clock at the start
+// of the call -- a function of the call lengths alone, kept by the host), its window is row joff of the 2 * bpc + 1 precomputed ones, and
+// tap i reads input trunc(i + j - 15.5): truncation toward zero (the reference's `0 | ...`), so input 0 is read twice where i + j - 15.5 is
+// -0.5 and +0.5.  That is why call boundaries show in the bytes and such a stream is a call-sequence stream.  The host only asks for outputs
+// whose taps lie inside the call (j + 15.5 < n_in, at most 31 samples back into the carried tail); the clamps keep a wrong record in bounds.
+LHIP_DEV void kb_resample_frac_elem(const Tables& T, float* dst, const int16_t* src, const float* old, double itime, int n_in, int64_t k) {
+    enum { BLACKSIZE = RS_TAPS - 1 };
+    const int bpc = T.rs_bpc;
+    const double time0 = (double)k * T.resample_ratio;
+    const int j = (int)floor(time0 - itime);
+    const double offset = (time0 - itime - (j + .5));
+    int joff = (int)floor((offset * 2 * bpc) + bpc + .5);
+    joff = joff < 0 ? 0 : (joff > 2 * bpc ? 2 * bpc : joff);
+    const float* coef = T.rs_blackfilt + (int64_t)joff * BLACKSIZE;
+    const bool do_scale = !(T.scale == 0.0) && !(T.scale == 1.0);
+    double xvalue = 0.0;
+    for (int i = 0; i < BLACKSIZE; i++) {
+        const int j2 = (int)(i + j - 15.5);
+        float y = 0.f;
+        if (j2 < 0) { if (j2 >= -BLACKSIZE) y = old[BLACKSIZE + j2]; }
+        else if (j2 < n_in) { y = (float)src[j2]; if (do_scale) y = (float)((double)y * T.scale); }
+        xvalue += (double)y * (double)coef[i];
+    }
+    dst[k] = (float)xvalue;
+}
+
 // Resampling configurations only: the new output-rate samples of every stream, grid-stride over (stream, channel, sample).
 // (Without resampling nothing is materialised: the consumers convert the caller's Int16 where they stage it, PcmSrc.)
 LHIP_DEV void kb_prep_stream(const Tables& T, const Workspace& W, const StreamDesc* SD, const StreamIO* IO, int st, int64_t tid, int64_t nthreads) {
@@ -169,7 +196,8 @@ LHIP_DEV void kb_prep_stream(const Tables& T, const Workspace& W, const StreamDe
     const int64_t off = SD[st].pcm_off + io.mf_size;
     for (int ch = 0; ch < C; ch++) {
         float* dst = W.pcm + (int64_t)ch * W.pcm_plane + off;
-        for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_elem(T, dst, (ch ? io.src[1] : io.src[0]), io.state->rs_old[ch], io.rs_p0, i);
+        if (T.rs_frac) for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_frac_elem(T, dst, (ch ? io.src[1] : io.src[0]), io.state->rs_old[ch], io.rs_itime, io.n_in, i);
+        else for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_elem(T, dst, (ch ? io.src[1] : io.src[0]), io.state->rs_old[ch], io.rs_p0, i);
     }
 }
 LHIP_DEV void kb_prep(const Tables& T, const Workspace& W, const StreamDesc* SD, const StreamIO* IO, int nstreams, int64_t tid, int64_t nthreads) {
@@ -1018,13 +1046,19 @@ static bool build_tables(TableSet& ts, const void* blob, size_t nbytes, const lh
     // ---- envelope checks: fail loudly rather than produce different bytes than the reference ----
     if (T.channels_out != (cfg.channels == 1 ? 1 : 2) || T.in_samplerate != cfg.samplerate || T.brate <= 0) { set_err("tables blob does not match the requested configuration"); return false; }
     // resampling (Lame.js:1849): only integer decimation ratios, where the reference's filter is a fixed 33-tap FIR
-    T.rs_ratio = 1;
+    // (extension: a blob built with { fractionalResample } carries the reference's set-up for a non-integer ratio -- filter_l = 31 and all
+    //  2 * bpc + 1 windows; such a stream is a call-sequence stream, see frac_pass)
+    T.rs_ratio = 1; T.rs_frac = 0;
     if (T.resample_ratio < .9999 || T.resample_ratio > 1.0001) {
         const int r = T.out_samplerate > 0 ? T.in_samplerate / T.out_samplerate : 0;
-        if (r < 2 || r * T.out_samplerate != T.in_samplerate || T.rs_filter_l != RS_TAPS - 1 || T.rs_bpc != 1) {
+        const lhtb_entry* bf = find_entry(b, "rs_blackfilt");
+        const bool nonint = !(fabs(T.resample_ratio - floor(.5 + T.resample_ratio)) < .0001);
+        if (T.rs_filter_l == RS_TAPS - 2 && nonint && T.out_samplerate > 0 && T.resample_ratio == (double)T.in_samplerate / T.out_samplerate &&
+            T.rs_bpc >= 1 && T.rs_bpc <= 320 && bf && bf->count == (uint32_t)(2 * T.rs_bpc + 1) * (RS_TAPS - 1) && T.disable_reservoir) {
+            T.rs_ratio = 0; T.rs_frac = 1;
+        } else if (r < 2 || r * T.out_samplerate != T.in_samplerate || T.rs_filter_l != RS_TAPS - 1 || T.rs_bpc != 1) {
             set_err("configuration outside the supported envelope (resampling by a non-integer ratio)"); return false;
-        }
-        T.rs_ratio = r;
+        } else T.rs_ratio = r;
     }
     if ((T.version != 1 && T.version != 0) || T.mode_gr != (T.version == 1 ? 2 : 1) || T.quant_comp != 9 || T.quant_comp_short != 9 || T.error_protection || T.sfb21_extra ||
         T.substep_shaping != 0 || T.noise_shaping_amp > 2 || T.use_best_huffman > 1 || T.athaa_loudapprox != 2 || T.full_outer_loop != 0) {
@@ -1274,6 +1308,11 @@ struct lhip_stream {
     int slot_lag = 0;
     int64_t frame_num = 0;
     int64_t rs_n_in = 0;           // resampling streams: input samples received so far
+    // non-integer ratio (Tables::rs_frac): what the reference's resampler carries from call to call besides the last 32 samples (device, rs_old)
+    double rs_itime = 0;           // gfc.itime (the same for both channels: it moves with the call lengths only)
+    double rs_inbuf_nsamples = 0;  // gfc.in_buffer_nsamples: the largest call so far (fractional after a flush bunch) ...
+    int64_t rs_inbuf_len = 0;      // ... and the length of the persistent input buffer allocated for it (Lame.js:1373-1379)
+    bool rs_flushed = false;       // flush() has run: the reference's resampler holds NaN from then on, the stream ends there
     ~lhip_stream() { rt::dfree(d_state); magic = 0; }
 };
 
@@ -1285,10 +1324,43 @@ struct Job {
     int F; int64_t bytes;
     int64_t n_out;              // samples this call appends to the encoder's buffer (== n unless resampling)
     bool flush = false;         // bit reservoir: the stream ends with this call (its bitstream is padded to the end of the last frame)
+    double rs_len = -1;         // non-integer ratio, flush only: the reference's (possibly fractional) length of this bunch of zeros; n = ceil(rs_len)
+    double rs_used = 0;         // non-integer ratio: num_used of the pass (== the call's length for every call that is accepted; a flush pass may end on a whole frame)
 };
 
 // resampling by the integer ratio r: output sample m exists once m*r + 16 < (input samples received) -- see kb_resample_elem
 static int64_t rs_outputs(int64_t n_in_total, int r) { return n_in_total > 16 ? (n_in_total - 16 + r - 1) / r : 0; }
+
+// Resampling by a non-integer ratio (extension { fractionalResample }).  One pass of fill_buffer_resample (Lame.js:1769-1813) over `len` input
+// samples with the clock at `itime`, as far as it depends on lengths only: how many outputs it delivers and how much input it uses, by the
+// reference's own loop in f64.  A pass that ends at the loop's `break` used the whole input (num_used == len); one that delivers a whole
+// frame first leaves num_used = j + 15.5 -- from then on the reference's buffer positions are fractional and its samples NaN.
+struct FracPass { int k; double num_used; int j_last; };
+static FracPass frac_pass(const Tables& T, double itime, double len) {
+    const int frame = 576 * T.mode_gr;
+    int k, j = 0;
+    for (k = 0; k < frame; k++) {
+        j = (int)floor(k * T.resample_ratio - itime);
+        if ((31 + j - 15.5) >= len) break;
+    }
+    const double reach = 31 + j - 15.5;
+    return FracPass{k, len < reach ? len : reach, j};
+}
+// a call of at most this many samples is consumed whole whatever came before: itime <= 15.5 after any whole pass
+static int64_t frac_call_limit(const Tables& T) { return (int64_t)floor((576 * T.mode_gr - 1) * T.resample_ratio - 15.5) + 15; }
+static std::string frac_refusal(const Tables& T, size_t n) {
+    return "fractionalResample: the reference does not consume a call of " + std::to_string(n) + " samples whole at this point of the stream (its resampler would turn to fractional "
+           "positions and NaN samples); nothing was consumed -- calls of at most " + std::to_string(frac_call_limit(T)) + " samples are always accepted for this configuration";
+}
+// the padding bit of the next frame and the accumulator after it (Encoder.js:442-446), as frame_padding / run_batch's bookkeeping have them
+static int host_next_padding(const Tables& T, int* slot_lag) {
+    if (T.frac_SpF == 0) return 0;
+    int64_t m = (int64_t)*slot_lag % T.out_samplerate; if (m < 0) m += T.out_samplerate;
+    const int pad = (m - T.frac_SpF) < 0 ? 1 : 0;
+    m = (m - T.frac_SpF) % T.out_samplerate; if (m < 0) m += T.out_samplerate;
+    *slot_lag = (int)m;
+    return pad;
+}
 
 static int64_t batch_bytes(const TableSet& ts, int slot_lag, int F) {
     int64_t npad = 0;
@@ -1343,6 +1415,12 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
         Job& j = jobs[i];
         lhip_stream* s = j.s;
         if (s->ts.get() != &ts) { set_err("batch: all streams must share one configuration"); return false; }
+        if (T.rs_frac) {                     // non-integer ratio: the outputs of this call by the reference's own loop; a call it would not consume whole is refused
+            FracPass fp = frac_pass(T, s->rs_itime, j.rs_len >= 0 ? j.rs_len : (double)j.n);
+            if (j.n == 0 && j.rs_len < 0) fp = FracPass{0, 0.0, 0};      // an empty call is no call (Lame.js:1497)
+            if ((fp.k >= frame && j.rs_len < 0) || (s->rs_flushed && j.n > 0)) { j.written = LHIP_ERR_INTERNAL; set_err(s->rs_flushed ? std::string("fractionalResample: the stream has been flushed") : frac_refusal(T, j.n)); return false; }
+            j.n_out = fp.k; j.rs_used = fp.num_used;
+        } else
         j.n_out = T.rs_ratio == 1 ? (int64_t)j.n : rs_outputs(s->rs_n_in + (int64_t)j.n, T.rs_ratio) - rs_outputs(s->rs_n_in, T.rs_ratio);
         const int64_t total = (int64_t)s->mf_size + j.n_out;
         if (total > 0x7fffffff || (int64_t)j.n > 0x7fffffff) { set_err("too many samples in one call"); return false; }
@@ -1430,7 +1508,8 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
         for (int k = 0; k <= GR * j.F; k++) gmap[sd[i].gslot0 + k] = i;
         StreamIO& o = io[i];
         o.state = j.s->d_state; o.n_new = (int)j.n_out; o.mf_size = j.s->mf_size; o.n_in = (int)j.n;
-        o.rs_p0 = T.rs_ratio == 1 ? 0 : (int)(rs_outputs(j.s->rs_n_in, T.rs_ratio) * T.rs_ratio - 16 - j.s->rs_n_in);
+        o.rs_p0 = T.rs_ratio <= 1 ? 0 : (int)(rs_outputs(j.s->rs_n_in, T.rs_ratio) * T.rs_ratio - 16 - j.s->rs_n_in);
+        o.rs_itime = j.s->rs_itime;
         out_rel[i] = sd[i].out_off;
         if (dev_io) {
             o.src[0] = j.l; o.src[1] = (C == 2 && j.r) ? j.r : j.l; o.out = j.out;
@@ -1783,6 +1862,11 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
             s->mf_samples_to_encode += (int)j.n_out;
         }
         s->rs_n_in += (int64_t)j.n;
+        if (T.rs_frac) {                     // Lame.js:1813 (num_used == the call's length: the pass used it whole), 1373-1379
+            const double len = j.rs_len >= 0 ? j.rs_len : (double)j.n;
+            s->rs_itime += j.rs_used - j.n_out * T.resample_ratio;
+            if (s->rs_inbuf_len == 0 || s->rs_inbuf_nsamples < len) { s->rs_inbuf_len = (int64_t)floor(len); s->rs_inbuf_nsamples = len; }
+        }
         s->mf_samples_to_encode -= frame * j.F;
         s->mf_size = (int)(total - (int64_t)frame * j.F);
         if (T.frac_SpF != 0 && j.F > 0) {
@@ -1941,7 +2025,9 @@ static int call_frames(const lhip_stream* s, size_t nsamples);
 int64_t lhip_encode_output_bytes(const lhip_stream* s, size_t nsamples) {
     if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
     if (!s->ts->T.disable_reservoir) return (int64_t)lhip_max_output_bytes(s, nsamples);      // data-dependent: only a bound exists
-    return batch_bytes(*s->ts, s->slot_lag, call_frames(s, nsamples));
+    const int F = call_frames(s, nsamples);
+    if (F < 0) { set_err(s->rs_flushed ? std::string("fractionalResample: the stream has been flushed") : frac_refusal(s->ts->T, nsamples)); return LHIP_ERR_INTERNAL; }      // the call would be refused
+    return batch_bytes(*s->ts, s->slot_lag, F);
 }
 
 int lhip_output_bytes_is_exact(const lhip_stream* s) {
@@ -1965,6 +2051,31 @@ static int encode_many(lhip_stream* const* streams, size_t n, const int16_t* con
     const Tables& T0 = streams[0]->ts->T;
     const bool resv = !T0.disable_reservoir;
     if (resv) for (size_t i = 0; i < n; i++) jobs[i].flush = flush_stream && ns[i] > 0;
+    // Non-integer-ratio streams (extension { fractionalResample }): a call the reference would not consume whole is refused before anything is
+    // consumed on ANY stream of the batch.  Their batches may mix configurations (a caller with many low-bitrate streams has one frame per
+    // stream and call at most): the streams are then launched configuration by configuration, in order of first appearance.
+    bool any_frac = false, mixed = false;
+    for (size_t i = 0; i < n; i++) { any_frac |= streams[i]->ts->T.rs_frac != 0; mixed |= streams[i]->ts.get() != streams[0]->ts.get(); }
+    if (any_frac) {
+        for (size_t i = 0; i < n; i++)
+            if (streams[i]->ts->T.rs_frac && ns[i] > 0 && call_frames(streams[i], ns[i]) < 0) {
+                set_err(streams[i]->rs_flushed ? std::string("fractionalResample: the stream has been flushed") : frac_refusal(streams[i]->ts->T, ns[i]));
+                for (size_t k = 0; k < n; k++) if (written) written[k] = LHIP_ERR_INTERNAL;
+                return LHIP_ERR_INTERNAL;
+            }
+        if (mixed) {
+            std::vector<char> done(n, 0);
+            for (size_t i = 0; i < n; i++) {
+                if (done[i]) continue;
+                std::vector<Job> group; std::vector<size_t> idx;
+                for (size_t k = i; k < n; k++) if (!done[k] && streams[k]->ts.get() == streams[i]->ts.get()) { group.push_back(jobs[k]); idx.push_back(k); done[k] = 1; }
+                const bool ok = run_batch(streams[0]->ctx, group, dev_io, true);
+                for (size_t g = 0; g < idx.size(); g++) if (written) written[idx[g]] = ok ? group[g].written : (group[g].written < 0 ? group[g].written : LHIP_ERR_INTERNAL);
+                if (!ok) { for (auto& j : group) if (j.written < 0) return (int)j.written; return LHIP_ERR_INTERNAL; }
+            }
+            return 0;
+        }
+    }
     const bool ok = run_batch(streams[0]->ctx, jobs, dev_io, sync || resv);
     for (size_t i = 0; i < n; i++) if (written) written[i] = ok ? jobs[i].written : (jobs[i].written < 0 ? jobs[i].written : LHIP_ERR_INTERNAL);
     if (!ok) { for (auto& j : jobs) if (j.written < 0) return (int)j.written; return LHIP_ERR_INTERNAL; }
@@ -2006,7 +2117,13 @@ static const ChunkSchedule& host_chunk_schedule() {
 static int call_frames(const lhip_stream* s, size_t nsamples) {
     const Tables& T = s->ts->T;
     const int frame = 576 * T.mode_gr, mf_needed = 1024 + frame - 272;
-    const int64_t n_out = T.rs_ratio == 1 ? (int64_t)nsamples : rs_outputs(s->rs_n_in + (int64_t)nsamples, T.rs_ratio) - rs_outputs(s->rs_n_in, T.rs_ratio);
+    int64_t n_out;
+    if (T.rs_frac) {                         // non-integer ratio: 0 or 1 frame, or -1 for a call that would be refused
+        if (nsamples == 0) return 0;
+        const FracPass fp = frac_pass(T, s->rs_itime, (double)nsamples);
+        if (fp.k >= frame || s->rs_flushed) return -1;
+        n_out = fp.k;
+    } else n_out = T.rs_ratio == 1 ? (int64_t)nsamples : rs_outputs(s->rs_n_in + (int64_t)nsamples, T.rs_ratio) - rs_outputs(s->rs_n_in, T.rs_ratio);
     const int64_t total = (int64_t)s->mf_size + n_out;
     return total >= mf_needed ? (int)((total - mf_needed) / frame) + 1 : 0;
 }
@@ -2200,7 +2317,7 @@ int64_t lhip_encode(lhip_stream* s, const int16_t* left, const int16_t* right, s
     {
         static const bool no_chunk = []() { const char* e = getenv("LAMEJS_HIP_NO_HOST_CHUNKS"); return e && e[0] == '1'; }();
         const Tables& T = s->ts->T;
-        if (!no_chunk && T.disable_reservoir && nsamples > (size_t)2 * host_chunk_schedule().first * 576 * T.mode_gr * T.rs_ratio) return encode_host_chunked(s, left, right, nsamples, out, out_cap);
+        if (!no_chunk && T.disable_reservoir && !T.rs_frac && nsamples > (size_t)2 * host_chunk_schedule().first * 576 * T.mode_gr * T.rs_ratio) return encode_host_chunked(s, left, right, nsamples, out, out_cap);
     }
     int64_t w = 0;
     const int rc = encode_many(&s, 1, &left, &right, &nsamples, &out, &out_cap, &w, false, true);
@@ -2246,8 +2363,129 @@ static size_t flush_zeros(lhip_stream* s) {
     return zeros;
 }
 
+// ---- flush of a non-integer-ratio stream (extension { fractionalResample }) ----
+// lame_encode_flush (Lame.js:1393-1443) feeds bunches of zeros of (mf_needed - mf_size) * in / out samples -- a fractional length -- until
+// frames_left bunches have each completed a frame.  Everything about it that depends on lengths only is mirrored here in f64: per fill pass
+// its outputs and num_used (frac_pass), and WHERE the reference's samples turn NaN: a tap or a carried-tail copy at a fractional position
+// (after a non-integer num_used) or beyond the end of its persistent input buffer (as long as the largest call so far) reads `undefined`.
+// A flush frame is CLEAN while no NaN lies in its input window [0, mf_needed): it is encoded by the kernels like any frame (the pass goes to
+// the device with its zeros and its fractional length).  From the first frame that is not, the reference encodes its own NaN samples
+// (near-empty frames); NaN never enters a kernel here -- those frames are emitted as silent frames of the reference's length and header.
+struct FracStep { double len; int k; bool device, frame, clean; int bytes, padding; };
+static bool frac_flush_plan(const lhip_stream* s, std::vector<FracStep>& steps) {
+    const Tables& T = s->ts->T;
+    const int frame = 576 * T.mode_gr, mf_needed = 1024 + frame - 272, B = RS_TAPS - 1;
+    steps.clear();
+    if (s->mf_samples_to_encode < 1) return true;
+    double samples_to_encode = s->mf_samples_to_encode - 1152;
+    samples_to_encode += 16. * T.out_samplerate / T.in_samplerate;
+    double end_padding = frame - fmod(samples_to_encode, (double)frame);
+    if (end_padding < 576) end_padding += frame;
+    double frames_left = (samples_to_encode + end_padding) / frame;
+    int mf = s->mf_size, lag = s->slot_lag, guard = 0;
+    double itime = s->rs_itime, inbuf_ns = s->rs_inbuf_nsamples;
+    int64_t inbuf_len = s->rs_inbuf_len;
+    bool old_nan[RS_TAPS - 1] = {false}, alive = true;
+    std::vector<char> mf_nan((size_t)mf_needed + 2 * frame + 64, 0);
+    auto in_nan = [&](double idx) { return idx != floor(idx) || idx < 0 || idx >= (double)inbuf_len; };      // inbuf[idx] is undefined -> NaN in a Float32Array
+    while (frames_left > 0) {
+        double bunch = mf_needed - mf;
+        bunch *= T.in_samplerate;
+        bunch /= T.out_samplerate;
+        if (bunch > 1152) bunch = 1152;
+        if (bunch < 1) bunch = 1;
+        if (inbuf_len == 0 || inbuf_ns < bunch) { inbuf_len = (int64_t)floor(bunch); inbuf_ns = bunch; }       // update_inbuffer_size: new Float32Array(bunch)
+        double nsamples = bunch, pos = 0;
+        bool emitted = false;
+        while (nsamples > 0) {
+            if (++guard > 256) { set_err("fractionalResample: the flush does not terminate"); return false; }
+            const double len = nsamples;
+            const FracPass fp = frac_pass(T, itime, len);
+            bool any_nan = false;
+            for (int k = 0; k < fp.k; k++) {
+                const int j = (int)floor(k * T.resample_ratio - itime);
+                bool nan = false;
+                for (int i = 0; i < B; i++) {
+                    const int j2 = (int)(i + j - 15.5);
+                    nan |= j2 < 0 ? (j2 >= -B ? old_nan[B + j2] : true) : in_nan(pos + j2);
+                }
+                mf_nan[(size_t)mf + k] = nan; any_nan |= nan;
+            }
+            {   // the carried tail (Lame.js:1816-1840), positions only
+                const double nu = fp.num_used;
+                bool nn[RS_TAPS - 1];
+                if (nu >= B) for (int i = 0; i < B; i++) nn[i] = in_nan(pos + nu + i - B);
+                else {
+                    const double n_shift = B - nu;
+                    int i = 0;
+                    for (; i < n_shift; ++i) { const double q = i + nu; nn[i] = (q != floor(q) || q >= B) ? true : old_nan[(int)q]; }
+                    for (int jj = 0; i < B; ++i, ++jj) nn[i] = in_nan(pos + jj);
+                }
+                memcpy(old_nan, nn, sizeof nn);
+                itime += nu - fp.k * T.resample_ratio;
+                nsamples -= nu; pos += nu;
+            }
+            FracStep st{len, fp.k, false, false, false, 0, 0};
+            const bool first = len == bunch;                                      // the pass starts at the bunch's first sample (a later one starts at a fractional position)
+            mf += fp.k;
+            st.frame = mf >= mf_needed;
+            if (st.frame) { st.clean = true; for (int p = 0; p < mf_needed; p++) if (mf_nan[p]) { st.clean = false; break; } }
+            st.device = alive && first && (st.frame ? st.clean : !any_nan);
+            if (st.frame && !st.device) st.clean = false;                        // (emitted as a silent frame)
+            if (!st.device || any_nan || fp.num_used != floor(fp.num_used)) alive = false;
+            if (st.frame) {
+                st.padding = host_next_padding(T, &lag);
+                st.bytes = s->ts->base_frame_bytes + st.padding;
+                mf -= frame;
+                memmove(mf_nan.data(), mf_nan.data() + frame, mf_nan.size() - frame);
+                emitted = true;
+            }
+            steps.push_back(st);
+        }
+        frames_left -= emitted ? 1 : 0;
+    }
+    return true;
+}
+static int64_t frac_flush(lhip_stream* s, uint8_t* out, size_t out_cap) {
+    const Tables& T = s->ts->T;
+    std::vector<FracStep> steps;
+    if (s->rs_flushed) return 0;
+    if (!frac_flush_plan(s, steps)) return LHIP_ERR_INTERNAL;
+    size_t total = 0;
+    for (const FracStep& st : steps) total += (size_t)st.bytes;
+    if (total > out_cap) { set_err("output buffer too small"); return LHIP_ERR_BUFFER_TOO_SMALL; }      // nothing was consumed
+    std::vector<int16_t> zeros(1152 + 8, 0);
+    int64_t w = 0;
+    for (const FracStep& st : steps) {
+        if (st.device) {
+            std::vector<Job> jobs(1);
+            jobs[0] = Job{s, zeros.data(), zeros.data(), (size_t)ceil(st.len), out + w, out_cap - (size_t)w, 0, 0, 0, 0};
+            jobs[0].rs_len = st.len;
+            if (!run_batch(s->ctx, jobs, false, true)) return jobs[0].written < 0 ? jobs[0].written : LHIP_ERR_INTERNAL;
+            if (jobs[0].written != st.bytes) { set_err("fractionalResample: the flush plan and the launch disagree"); return LHIP_ERR_INTERNAL; }
+            w += jobs[0].written;
+        } else if (st.frame) {
+            // a silent frame: the header the reference writes (BitStream.js:259-281; mode_ext 0), side information and main data zero
+            uint8_t* f = out + w;
+            memset(f, 0, (size_t)st.bytes);
+            const int sync = T.out_samplerate < 16000 ? 0xffe : 0xfff;
+            f[0] = (uint8_t)(sync >> 4);
+            f[1] = (uint8_t)(((sync & 15) << 4) | (T.version << 3) | (1 << 1) | (T.error_protection ? 0 : 1));
+            f[2] = (uint8_t)((T.bitrate_index << 4) | (T.samplerate_index << 2) | (st.padding << 1) | T.extension);
+            f[3] = (uint8_t)((T.mode << 6) | (T.copyright << 3) | (T.original << 2) | T.emphasis);
+            int lag = s->slot_lag; (void)host_next_padding(T, &lag); s->slot_lag = lag;
+            s->frame_num++;
+            w += st.bytes;
+        }
+    }
+    s->mf_samples_to_encode = 0;
+    s->rs_flushed = true;
+    return w;
+}
+
 int64_t lhip_flush(lhip_stream* s, uint8_t* out, size_t out_cap) {
     if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    if (s->ts->T.rs_frac) return frac_flush(s, out, out_cap);
     const size_t z = flush_zeros(s);
     if (z == 0) { s->mf_samples_to_encode = 0; return 0; }
     std::vector<int16_t> zeros(z, 0);
@@ -2272,7 +2510,7 @@ int lhip_encode_batch(lhip_stream* const* streams, size_t nstreams, const int16_
             if (ok) for (size_t k = 0; k < i; k++) if (streams[k] == streams[i]) { ok = false; break; }      // (a handle twice in one batch: the plain path reports it)
             total += nsamples[i];
         }
-        if (ok && streams[0]->ts->T.disable_reservoir) {
+        if (ok && streams[0]->ts->T.disable_reservoir && !streams[0]->ts->T.rs_frac) {
             const Tables& T = streams[0]->ts->T;
             if (total > (size_t)4 * host_chunk_schedule().first * 576 * T.mode_gr * T.rs_ratio) return encode_host_groups(streams, nstreams, left, right, nsamples, out, out_cap, written);
         }
@@ -2284,6 +2522,17 @@ int lhip_flush_batch(lhip_stream* const* streams, size_t nstreams, uint8_t* cons
     std::vector<std::vector<int16_t>> zs(nstreams);
     std::vector<const int16_t*> l(nstreams);
     std::vector<size_t> ns(nstreams);
+    bool any_frac = false;
+    for (size_t i = 0; i < nstreams; i++) any_frac |= streams[i] && streams[i]->magic == 0x4c484950 && streams[i]->ts->T.rs_frac;
+    if (any_frac) {                          // non-integer-ratio streams end with a few frames each, partly made on the host (frac_flush): one after the other
+        int rc = 0;
+        for (size_t i = 0; i < nstreams; i++) {
+            const int64_t w = lhip_flush(streams[i], out[i], out_cap[i]);
+            if (written) written[i] = w;
+            if (w < 0 && rc == 0) rc = (int)w;
+        }
+        return rc;
+    }
     for (size_t i = 0; i < nstreams; i++) {
         if (!streams[i] || streams[i]->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
         ns[i] = flush_zeros(streams[i]);
@@ -2318,6 +2567,7 @@ size_t lhip_state_bytes(const lhip_stream* s) {
 }
 int lhip_state_get(lhip_stream* s, void* buf, size_t cap) {
     if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    if (s->ts->T.rs_frac) { set_err("lhip_state_get: not for fractionalResample streams (call-sequence streams: the resampler's clock is not part of the state record)"); return LHIP_ERR_INTERNAL; }
     if (!buf || cap < lhip_state_bytes(s)) { set_err("state buffer too small"); return LHIP_ERR_BUFFER_TOO_SMALL; }
     Context* ctx = s->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -2346,6 +2596,7 @@ int lhip_state_get(lhip_stream* s, void* buf, size_t cap) {
 int lhip_state_set(lhip_stream* s, const void* buf, size_t n) {
     if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
     StateHdr h;
+    if (s->ts->T.rs_frac) { set_err("lhip_state_set: not for fractionalResample streams"); return LHIP_ERR_INTERNAL; }
     if (!buf || n < sizeof h) { set_err("state blob too small"); return LHIP_ERR_INTERNAL; }
     memcpy(&h, buf, sizeof h);
     Context* ctx = s->ctx;
@@ -2392,6 +2643,32 @@ int lhip_seek(lhip_stream* s, int64_t sample_pos, const int16_t* tail_left, cons
         s->slot_lag = (int)m;
     }
     return 0;
+}
+
+// Test hooks (extension { fractionalResample }): the host arithmetic of a non-integer-ratio stream alone, nothing is encoded or consumed.
+int64_t lhip_frac_call_limit(const lhip_stream* s) {
+    if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    return s->ts->T.rs_frac ? frac_call_limit(s->ts->T) : 0;
+}
+int lhip_debug_frac_call(const lhip_stream* s, size_t nsamples, int32_t* k, int32_t* frames) {
+    if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    const Tables& T = s->ts->T;
+    if (!T.rs_frac) { set_err("not a fractionalResample stream"); return LHIP_ERR_INTERNAL; }
+    const FracPass fp = frac_pass(T, s->rs_itime, (double)nsamples);
+    if (k) *k = fp.k;
+    const int F = call_frames(s, nsamples);
+    if (frames) *frames = F;
+    if (F < 0) { set_err(frac_refusal(T, nsamples)); return LHIP_ERR_INTERNAL; }
+    return 0;
+}
+int lhip_debug_frac_flush(const lhip_stream* s, int32_t* bytes, int32_t* clean, int cap) {
+    if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    if (!s->ts->T.rs_frac) { set_err("not a fractionalResample stream"); return LHIP_ERR_INTERNAL; }
+    std::vector<FracStep> steps;
+    if (!frac_flush_plan(s, steps)) return LHIP_ERR_INTERNAL;
+    int n = 0;
+    for (const FracStep& st : steps) if (st.frame) { if (n < cap) { if (bytes) bytes[n] = st.bytes; if (clean) clean[n] = st.clean ? 1 : 0; } n++; }
+    return n;
 }
 
 // Test hook (aliased contexts, LHIP_ALIAS_DEVICES): gives back what context `device` holds beyond its streams' lifetime -- the HIP stream the library created

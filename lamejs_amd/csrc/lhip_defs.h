@@ -86,7 +86,8 @@ struct Tables {
         n_s3_ll,                            // entries of s3_ll (the long-block spreading rows back to back): g_psyB stages them in LDS
        
         in_samplerate, rs_filter_l, rs_bpc,
-        rs_ratio,                           // integer decimation factor (1 = no resampling), derived at create time
+        rs_ratio,                           // integer decimation factor (1 = no resampling; 0 with rs_frac), derived at create time
+        rs_frac,                            // 1: resampling by a non-integer ratio (extension: filter_l = 31, all 2 * bpc + 1 windows in use; kb_resample_frac_elem)
         psy_channels,                       // channels the psychoacoustic model analyses: channels_out, or 4 (L, R, mid, side) in joint stereo (mode == 1)
         disable_reservoir;                  // 1 on the Mp3Encoder path (index.js:108); 0 = the bit-reservoir extension: one frame per stream and launch
     // scalars (doubles)

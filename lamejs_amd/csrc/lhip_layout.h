@@ -82,6 +82,7 @@ struct StreamIO {          // per stream, per launch (device array parallel to S
     int32_t n_new, mf_size;    // samples appended to the encoder's buffer by this call / already buffered
     int32_t n_in, rs_p0;       // resampling streams: input samples of this call; input position (relative to this call's
                                // first sample, >= -32) of tap 0 of the first new output sample
+    double rs_itime;           // non-integer ratio: the resampler's clock for this call (Lame.js:1767, 1813); kept by the host, it depends on call lengths only
 };
 
 // Where the samples of a stream's segment (carried tail ++ this call's new samples) come from.  Without resampling nothing is

@@ -40,6 +40,7 @@ static int (*p_state_get)(lhip_stream*, void*, size_t);
 static int (*p_state_set)(lhip_stream*, const void*, size_t);
 static size_t (*p_seek_tail)(const lhip_stream*);
 static int (*p_seek)(lhip_stream*, int64_t, const int16_t*, const int16_t*);
+static int64_t (*p_call_limit)(const lhip_stream*);
 
 static int load_lib(napi_env env) {
     if (g_lib) return 1;
@@ -61,6 +62,7 @@ static int load_lib(napi_env env) {
     SYM(p_encode_batch, "lhip_encode_batch") SYM(p_flush_batch, "lhip_flush_batch") SYM(p_set_devices, "lhip_set_devices")
     SYM(p_state_bytes, "lhip_state_bytes") SYM(p_state_get, "lhip_state_get") SYM(p_state_set, "lhip_state_set")
     SYM(p_seek_tail, "lhip_seek_tail_samples") SYM(p_seek, "lhip_seek") SYM(p_out_bytes, "lhip_encode_output_bytes")
+    SYM(p_call_limit, "lhip_frac_call_limit")
 #undef SYM
     return 1;
 }
@@ -122,6 +124,9 @@ static napi_value encode_into_new_array(napi_env env, lhip_stream* s, const int1
     static uint8_t none[16];
     const int64_t want = p_out_bytes(s, nl);
     const size_t cap = want > 0 ? (size_t)want : 0;
+    /* { fractionalResample } streams: a call the reference would not consume whole is refused before anything is consumed -- there is no reference
+     * behaviour to mirror for it (its own output is made of NaN samples from there on), so it throws with the library's explanation */
+    if (want == -4 && p_call_limit(s) > 0) { napi_throw_range_error(env, NULL, p_last_error()); return NULL; }
     if (cap > 0 && p_is_exact(s) != 1) {
         /* the count is an upper bound, not the count (bit-reservoir extension): encode into scratch memory and hand out an exact copy -- a
          * zero-filled ArrayBuffer of the bound per call would be allocated only to be thrown away */
@@ -245,6 +250,14 @@ static lhip_stream* handle_arg(napi_env env, napi_value v) {
     if (napi_get_value_external(env, v, (void**)&s) != napi_ok || !s) { napi_throw_type_error(env, NULL, "first argument must be a stream handle"); return NULL; }
     return s;
 }
+static napi_value js_call_limit(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1], r;
+    napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
+    lhip_stream* s = argc >= 1 ? handle_arg(env, argv[0]) : NULL;
+    if (!s) return NULL;
+    napi_create_int64(env, p_call_limit(s), &r);
+    return r;
+}
 static napi_value js_seek_tail(napi_env env, napi_callback_info info) {
     size_t argc = 1; napi_value argv[1], r;
     napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
@@ -301,7 +314,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"encode", 0, js_encode, 0, 0, 0, napi_default, 0}, {"flush", 0, js_flush, 0, 0, 0, napi_default, 0},
         {"encodeBatch", 0, js_encode_batch, 0, 0, 0, napi_default, 0}, {"flushBatch", 0, js_flush_batch, 0, 0, 0, napi_default, 0},
         {"setDevices", 0, js_set_devices, 0, 0, 0, napi_default, 0},
-        {"seekTailSamples", 0, js_seek_tail, 0, 0, 0, napi_default, 0}, {"seek", 0, js_seek, 0, 0, 0, napi_default, 0},
+        {"seekTailSamples", 0, js_seek_tail, 0, 0, 0, napi_default, 0}, {"callLimit", 0, js_call_limit, 0, 0, 0, napi_default, 0}, {"seek", 0, js_seek, 0, 0, 0, napi_default, 0},
         {"stateGet", 0, js_state_get, 0, 0, 0, napi_default, 0}, {"stateSet", 0, js_state_set, 0, 0, 0, napi_default, 0}};
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;

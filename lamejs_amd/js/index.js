@@ -20,6 +20,13 @@
  * sixty-four together take hardly longer.  The BYTE STREAM is the reference's (any chunking of the samples gives the same bytes); only
  * WHICH call returns which bytes changes: calls return empty arrays until N frames are pending, then all their frames at once, and
  * flush() returns the rest.  Off by default: without it every call returns exactly the bytes the reference's call returns.
+ * Extension { fractionalResample: true }: the 49 (channels, sample rate, kbps) triples the reference resamples by a non-integer ratio -- refused
+ * by default, because the reference feeds itself NaN samples there once a call is long enough -- are accepted as call-sequence streams: every
+ * encodeBuffer() gives the reference's bytes for the same sequence of call lengths; a call longer than the reference consumes whole throws
+ * (enc.callLimit() samples are always accepted: 1585 for 44100 -> 32000 Hz, never less than 576); a call completes at most one frame -- the
+ * throughput is in encodeBatch() over many such streams, of any mix of configurations; the flush frames the reference makes of its own NaN
+ * samples are replaced by silent frames of equal length and header, and the stream ends with flush().  Not with { pendingFrames }
+ * (re-chunking changes the bytes) or { reservoir }; no seek / getState / setState.  For every other triple the option changes nothing.
  */
 'use strict';
 const path = require('path');
@@ -37,7 +44,7 @@ function loadAddon() {
  * between streams with identical blobs as well).  Configurations outside the envelope throw in buildBlob and are not cached. */
 const blobCache = new Map();
 function tablesBlob(channels, samplerate, kbps, opts) {
-    const key = [channels, samplerate, kbps, opts && opts.jointStereo ? 1 : 0, opts && opts.reservoir ? 1 : 0].join('|');     /* (pendingFrames is host-side only) */
+    const key = [channels, samplerate, kbps, opts && opts.jointStereo ? 1 : 0, opts && opts.reservoir ? 1 : 0, opts && opts.fractionalResample ? 1 : 0].join('|');     /* (pendingFrames is host-side only) */
     let blob = blobCache.get(key);
     if (!blob) { blob = tables.buildBlob(channels, samplerate, kbps, opts).blob; blobCache.set(key, blob); }
     return blob;
@@ -51,6 +58,10 @@ function Mp3Encoder(channels, samplerate, kbps, opts) {
     }
     const native = loadAddon();
     const blob = tablesBlob(channels, samplerate, kbps, opts);
+    /* a stream that resamples by a non-integer ratio is a call-sequence stream: holding input back would change its bytes */
+    const fractional = !!(opts && opts.fractionalResample) && tables.fractionalCallLimit(tables.resolveParams(channels, samplerate, kbps, opts)) > 0;
+    if (fractional && opts.pendingFrames > 1)
+        throw new Error('lamejs_amd: { pendingFrames } cannot be combined with { fractionalResample } for (' + channels + ',' + samplerate + ',' + kbps + '): the bytes of such a stream depend on the call lengths');
     const handle = native.create(blob, channels, samplerate, kbps, defaultDevice);
     const hooks = { handle: handle, channels: channels, drain: null, pending: () => 0 };
     Object.defineProperty(this, '_lhip', { value: hooks, enumerable: false });
@@ -98,6 +109,8 @@ function Mp3Encoder(channels, samplerate, kbps, opts) {
     this.seek = function (samplePos, tailLeft, tailRight) { noPending('seek'); native.seek(handle, samplePos, tailLeft, channels == 1 ? null : (tailRight || null)); };
     this.getState = function () { noPending('getState'); return native.stateGet(handle); };
     this.setState = function (state) { noPending('setState'); native.stateSet(handle, state); };
+    /* { fractionalResample }: the encodeBuffer() length that is accepted whatever calls came before (0: any length goes) */
+    this.callLimit = function () { return native.callLimit(handle); };
 }
 
 /* RIFF/WAVE header reader with the reference's field names (index.js:138-193) */
@@ -134,7 +147,7 @@ module.exports.deviceCount = function () { return loadAddon().deviceCount(); };
  *                                         bytes each encoder's own encodeBuffer() would have returned
  *   flushBatch(encoders)                  likewise for flush()
  *   setDevices(mask)                      let the library deal new encoders round-robin over the GPUs named by the bit mask
- * The encoders of one call must share (channels, samplerate, kbps) and the device.
+ * The encoders of one call must share (channels, samplerate, kbps) and the device ({ fractionalResample } streams: the device only).
  */
 module.exports.setDevice = function (d) { defaultDevice = d | 0; };
 /* setDevices(mask): bit d = HIP device d may be used; encoders constructed with the default device (-1) are then dealt round-robin

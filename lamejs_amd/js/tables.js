@@ -20,7 +20,8 @@
  *
  * Supported envelope (everything else throws): CBR, every MPEG-1 / MPEG-2 / MPEG-2.5 sample rate
  * 1 or 2 channels, with out_samplerate == in_samplerate or an integer multiple below it (resampling by a non-integer
- * ratio makes the reference feed itself NaN samples; refused).
+ * ratio makes the reference feed itself NaN samples; refused unless { fractionalResample: true } asks for the call-sequence-exact
+ * extension, see resolveParams).
  */
 'use strict';
 
@@ -92,17 +93,23 @@ function resolveParams(channels, samplerate, kbps, opts) {
     p.out_samplerate = out_samplerate;
     p.lowpassfreq = lowpassfreq;
 
-    /* resampler set-up (Lame.js:943, 1719-1763).  Only integer ratios are in the envelope: for any other ratio the
-     * reference's filter_l / 2 is 15.5, its buffer positions become fractional, typed-array reads return undefined and
-     * the encoder is fed NaN samples (at the latest in flush()) -- there is no well-defined output to reproduce. */
+    /* resampler set-up (Lame.js:943, 1719-1763).  By default only integer ratios are in the envelope: for any other ratio the
+     * reference's filter_l / 2 is 15.5, and once a fill pass delivers a whole frame its buffer positions become fractional, typed-array
+     * reads return undefined and the encoder is fed NaN samples (at the latest in flush()).
+     * extension { fractionalResample: true }: such a configuration is accepted as a CALL-SEQUENCE stream -- every encodeBuffer() call the
+     * reference consumes whole (always true up to fractionalCallLimit() samples) gives the reference's bytes for the same sequence of
+     * call lengths; longer calls are refused (DESIGN_EXTENSIONS.md 5). */
     p.resample_ratio = samplerate / out_samplerate;
     p.rs_filter_l = 0; p.rs_bpc = 0; p.rs_blackfilt = f32(1);
     if (p.resample_ratio < .9999 || p.resample_ratio > 1.0001) {
         const ratio = p.resample_ratio;
         const intratio = (Math.abs(ratio - Math.floor(.5 + ratio)) < .0001) ? 1 : 0;
-        if (!intratio)
+        if (!intratio && !(opts && opts.fractionalResample))
             throw new Error('lamejs_amd: (' + channels + ',' + samplerate + ',' + kbps + ') would resample to ' + out_samplerate +
-                ' Hz by the non-integer ratio ' + ratio + '; the reference feeds itself NaN samples there (fractional buffer positions), not supported');
+                ' Hz by the non-integer ratio ' + ratio + '; the reference feeds itself NaN samples there (fractional buffer positions), not supported' +
+                ' without the option { fractionalResample: true } (call-sequence-exact, calls of limited length)');
+        if (!intratio && opts.reservoir)
+            throw new Error('lamejs_amd: { fractionalResample } and { reservoir } cannot be combined');
         const gcd = (i, j) => (j != 0 ? gcd(j, i % j) : i);
         let bpc = out_samplerate / gcd(out_samplerate, samplerate);
         if (bpc > 320) bpc = 320;                                            /* LameInternalFlags.BPC */
@@ -665,12 +672,20 @@ function sourceHash() {
     return Int32Array.from([d.readInt32LE(0), d.readInt32LE(4)]);
 }
 
-module.exports = { buildBlob, resolveParams, buildTables, packBlob, sourceHash };
+/* { fractionalResample }: the longest encodeBuffer() call that is accepted whatever calls came before (0: the configuration does not
+ * resample by a non-integer ratio, any length goes).  The reference consumes a call whole while floor((framesize - 1) * ratio - itime)
+ * + 15.5 >= length, and its clock itime never exceeds 15.5 after a call it consumed whole (Lame.js:1769-1813). */
+function fractionalCallLimit(p) {
+    if (p.rs_filter_l != 31) return 0;
+    return Math.floor((p.framesize - 1) * p.resample_ratio - 15.5) + 15;
+}
+
+module.exports = { buildBlob, resolveParams, buildTables, packBlob, sourceHash, fractionalCallLimit };
 
 if (require.main === module) {
-    /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] */
+    /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] [fracresample] */
     const [ch, sr, kb, out] = process.argv.slice(2), flags = process.argv.slice(6);
-    const r = buildBlob(+ch, +sr, +kb, { jointStereo: flags.includes('joint'), reservoir: flags.includes('reservoir') });
+    const r = buildBlob(+ch, +sr, +kb, { jointStereo: flags.includes('joint'), reservoir: flags.includes('reservoir'), fractionalResample: flags.includes('fracresample') });
     require('fs').writeFileSync(out, r.blob);
     console.log('wrote', out, r.blob.length, 'bytes');
 }
