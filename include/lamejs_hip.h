@@ -36,6 +36,9 @@
  * of equal length and header; the stream ends with its flush (a later lhip_encode returns -4).  lhip_seek, lhip_state_get and lhip_state_set
  * return -4 for such streams; the bit reservoir cannot be combined with it.  lhip_encode_batch over such streams may mix configurations.
  *
+ * Sample formats.  lhip_encode takes Int16 planes; lhip_encode_pcm and the *_pcm batch entries take Int16 or Float32, planar or interleaved
+ * (see LHIP_PCM_* below): Float32 is what the reference itself encodes, so fractional samples and samples beyond 16 bits give its bytes.
+ *
  * Semantics preserved: any chunking of the same sample stream yields the same bytes; a call
  * returns the bytes of all whole frames completed by that call (possibly 0); errors are negative
  * return codes mirroring the reference (-1 output buffer too small, -3 bad handle, -4 internal/device
@@ -112,6 +115,26 @@ int lhip_create(const lhip_config* cfg, const void* tables, size_t tables_bytes,
 int64_t lhip_encode(lhip_stream* s, const int16_t* left, const int16_t* right, size_t nsamples,
                     uint8_t* out, size_t out_cap);
 
+/* Sample formats (extension).  The reference's encodeBuffer stores whatever numbers it is given into a Float32Array and encodes those
+ * (Lame.js:1506-1510); PCM on disk and on the wire is interleaved.  A format is a sample type, LHIP_PCM_S16 or LHIP_PCM_F32, optionally
+ * or-ed with LHIP_PCM_INTERLEAVED; one format per call, any format at any call of a stream.  The *_pcm entries below are the entries
+ * above them with a format: the old entries ARE their LHIP_PCM_S16 planar case.
+ *   F32: the sample is used as the Float32 it is (then `gfp.scale` where it applies: (float)((double)v * scale), as for Int16).  For
+ *        integer values inside the Int16 range the bytes are those of the Int16 call.
+ *   INTERLEAVED: left points at channels * nsamples samples (L R L R ...), right is ignored; byte for byte the result of the planar call
+ *        on the de-interleaved samples.  For a one-channel stream interleaved is planar.  nsamples always counts samples per channel.
+ * The one deviation from the reference: every F32 sample must be finite with |x| <= 131072.0 (four times Int16 full scale).  The
+ * reference encodes NaN and infinities into garbage; here they never reach a kernel.  Host-pointer entries look at the whole call first:
+ * a bad sample gives -4, lhip_last_error() names stream, channel, index and value, and nothing is consumed on any stream.  The
+ * device-pointer entry cannot see the values: every read site reads such a sample as 0.0f, and lhip_last_batch_rejected_samples()
+ * reports how many (stream, channel, sample) positions of the calling thread's last batch were read that way (it synchronises).
+ * lhip_seek keeps its Int16 tails; state blobs do not depend on the formats that produced them. */
+#define LHIP_PCM_S16         0
+#define LHIP_PCM_F32         1
+#define LHIP_PCM_INTERLEAVED 2
+int64_t lhip_encode_pcm(lhip_stream* s, int format, const void* left, const void* right, size_t nsamples,
+                        uint8_t* out, size_t out_cap);
+
 /* Pad with zeros until all buffered samples are emitted (reference flush rules); a second call
  * returns 0. */
 int64_t lhip_flush(lhip_stream* s, uint8_t* out, size_t out_cap);
@@ -137,6 +160,9 @@ int lhip_output_bytes_is_exact(const lhip_stream* s);
 int lhip_encode_batch(lhip_stream* const* streams, size_t nstreams, const int16_t* const* left,
                       const int16_t* const* right, const size_t* nsamples, uint8_t* const* out,
                       const size_t* out_cap, int64_t* written);
+int lhip_encode_batch_pcm(lhip_stream* const* streams, size_t nstreams, int format, const void* const* left,
+                          const void* const* right, const size_t* nsamples, uint8_t* const* out,
+                          const size_t* out_cap, int64_t* written);
 int lhip_flush_batch(lhip_stream* const* streams, size_t nstreams, uint8_t* const* out,
                      const size_t* out_cap, int64_t* written);
 
@@ -151,6 +177,15 @@ int lhip_flush_batch(lhip_stream* const* streams, size_t nstreams, uint8_t* cons
 int lhip_encode_batch_device(lhip_stream* const* streams, size_t nstreams, const int16_t* const* d_left,
                              const int16_t* const* d_right, const size_t* nsamples, uint8_t* const* d_out,
                              const size_t* out_cap, int64_t* written, int sync);
+
+int lhip_encode_batch_device_pcm(lhip_stream* const* streams, size_t nstreams, int format, const void* const* d_left,
+                                 const void* const* d_right, const size_t* nsamples, uint8_t* const* d_out,
+                                 const size_t* out_cap, int64_t* written, int sync);
+/* F32 samples outside the contract that the last lhip_encode_batch_device_pcm of the calling thread read as zero (0 after any other call);
+ * waits for that batch.  A two-channel planar call whose right plane is NULL or the left plane counts each sample once.  The counter lives with the
+ * device context: fetch it before another thread starts a Float32 device batch on the same device (a handle is not thread-safe, and neither
+ * is this pairing of a batch with its count).  < 0: device error. */
+int64_t lhip_last_batch_rejected_samples(void);
 
 /* Use this hipStream_t (passed as void*) for all work of streams on `device` (-1 = current). */
 int lhip_set_hip_stream(int device, void* hip_stream);

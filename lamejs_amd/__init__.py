@@ -22,7 +22,10 @@ _PKG = Path(__file__).resolve().parent
 _LIB_PATH = _PKG / "lib" / "liblamejs_hip.so"
 _TABLE_DIR = _PKG / "tables"
 
-__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams"]
+__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED"]
+
+# sample formats of the *_pcm entries (include/lamejs_hip.h: LHIP_PCM_*): a sample type, optionally or-ed with PCM_INTERLEAVED
+PCM_S16, PCM_F32, PCM_INTERLEAVED = 0, 1, 2
 
 
 class LhipError(RuntimeError):
@@ -64,6 +67,15 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
     lib.lhip_output_bytes_is_exact.argtypes = [ctypes.c_void_p]
     for name in ("lhip_encode_batch", "lhip_flush_batch", "lhip_encode_batch_device"):
         getattr(lib, name).restype = ctypes.c_int
+    # sample formats: a library without these entries is not this package's library (no fallback to the Int16 entries)
+    lib.lhip_encode_pcm.restype = ctypes.c_int64
+    lib.lhip_encode_pcm.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+    lib.lhip_encode_batch_pcm.restype = ctypes.c_int
+    lib.lhip_encode_batch_pcm.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int] + [ctypes.c_void_p] * 6
+    lib.lhip_encode_batch_device_pcm.restype = ctypes.c_int
+    lib.lhip_encode_batch_device_pcm.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int]
+    lib.lhip_last_batch_rejected_samples.restype = ctypes.c_int64
+    lib.lhip_last_batch_rejected_samples.argtypes = []
     lib.lhip_set_hip_stream.restype = ctypes.c_int
     lib.lhip_set_hip_stream.argtypes = [ctypes.c_int, ctypes.c_void_p]
     lib.lhip_last_batch_stats.restype = None
@@ -138,6 +150,26 @@ def _as_i16(a) -> np.ndarray:
     return arr
 
 
+def _as_pcm(a):
+    """(array, sample type) of one PCM argument: integer dtypes go in as Int16 as they always did, floating dtypes as Float32 --
+    which is what the reference's encodeBuffer makes of any numbers it is given (Lame.js:1506-1510)."""
+    arr = np.asarray(a)
+    if arr.dtype.kind == "f":
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        if arr.ndim != 1:
+            raise ValueError("PCM must be a 1-D array")
+        return arr, PCM_F32
+    return _as_i16(arr), PCM_S16
+
+
+def _same_type(arrs):
+    """Arrays of one call share one sample type: Float32 if any of them is floating (Int16 values are exact in Float32)."""
+    pairs = [_as_pcm(a) for a in arrs]
+    if all(t == PCM_S16 for _, t in pairs):
+        return [a for a, _ in pairs], PCM_S16
+    return [np.ascontiguousarray(a, dtype=np.float32) for a, _ in pairs], PCM_F32
+
+
 class Mp3Encoder:
     """Mirror of the reference's ``Mp3Encoder`` (index.js:66-136)."""
 
@@ -208,20 +240,41 @@ class Mp3Encoder:
             raise LhipError(f"lhip_state_set failed ({rc}): {self._lib.lhip_last_error().decode()}")
 
     def encodeBuffer(self, left, right=None) -> bytes:
-        l = _as_i16(left)
-        r = l if (self.channels == 1 or right is None) else _as_i16(right)
+        """Integer arrays are encoded as Int16 (lhip_encode, as always); floating arrays as the Float32 values they are (lhip_encode_pcm),
+        fractional parts and values beyond 16 bits included -- the reference's bytes for the same numbers.  A floating sample that is not
+        finite or lies beyond +-131072 raises and consumes nothing."""
+        if self.channels == 1 or right is None:
+            (l,), fmt = _same_type([left])
+            r = l
+        else:
+            (l, r), fmt = _same_type([left, right])
         if len(l) != len(r):
             raise ValueError("left/right length mismatch")
-        if len(l) == 0:
+        return self._encode(fmt, l, r, len(l))
+
+    def encode_interleaved(self, samples) -> bytes:
+        """Extension: ``channels * n`` samples as they lie in a WAV file (L R L R ...), Int16 or floating; the bytes of ``encodeBuffer`` on the
+        de-interleaved samples."""
+        (a,), fmt = _same_type([samples])
+        if len(a) % self.channels:
+            raise ValueError("interleaved PCM: the length is not a multiple of the channel count")
+        return self._encode(fmt | PCM_INTERLEAVED, a, a, len(a) // self.channels)
+
+    def _encode(self, fmt, l, r, nsamples) -> bytes:
+        if nsamples == 0:
             return b""
         # the N-API binding's protocol: the result array is allocated at lhip_encode_output_bytes() and written in place
-        cap = self._lib.lhip_encode_output_bytes(self._h, len(l))
+        cap = self._lib.lhip_encode_output_bytes(self._h, nsamples)
         if cap < 0:
             raise LhipError(f"lhip_encode_output_bytes failed ({cap}): {self._lib.lhip_last_error().decode()}")
         out = np.empty(cap, dtype=np.uint8)
-        n = self._lib.lhip_encode(self._h, l.ctypes.data, r.ctypes.data, len(l), out.ctypes.data, cap)
+        entry = "lhip_encode" if fmt == PCM_S16 else "lhip_encode_pcm"
+        if fmt == PCM_S16:
+            n = self._lib.lhip_encode(self._h, l.ctypes.data, r.ctypes.data, nsamples, out.ctypes.data, cap)
+        else:
+            n = self._lib.lhip_encode_pcm(self._h, fmt, l.ctypes.data, r.ctypes.data, nsamples, out.ctypes.data, cap)
         if n < 0:
-            raise LhipError(f"lhip_encode failed ({n}): {self._lib.lhip_last_error().decode()}")
+            raise LhipError(f"{entry} failed ({n}): {self._lib.lhip_last_error().decode()}")
         if self._lib.lhip_output_bytes_is_exact(self._h) == 1 and n != cap:      # exact without the bit reservoir: that is what lets a binding skip the copy
             raise LhipError(f"lhip_encode returned {n} bytes, lhip_encode_output_bytes promised {cap}")
         return out[:n].tobytes()
@@ -251,27 +304,36 @@ class Mp3Encoder:
             pass
 
 
-def encode_streams(encoders, lefts, rights=None, flush=True):
+def encode_streams(encoders, lefts, rights=None, flush=True, interleaved=False):
     """Batch extension (BASELINE config 5): one launch for many independent streams.
 
-    encoders: list of Mp3Encoder with identical configuration (``fractional_resample`` streams may mix configurations); lefts/rights: per-stream Int16 arrays.
+    encoders: list of Mp3Encoder with identical configuration (``fractional_resample`` streams may mix configurations); lefts/rights: per-stream arrays.
+    Int16 if every array is of an integer dtype, otherwise the whole batch as Float32 -- still one launch.  ``interleaved``: ``lefts[i]``
+    holds ``channels * n`` samples (L R L R ...), ``rights`` is ignored.
     Returns a list of bytes objects (encode [+ flush] output per stream)."""
     lib = encoders[0]._lib
     n = len(encoders)
-    L = [_as_i16(a) for a in lefts]
-    R = L if rights is None else [_as_i16(a) for a in rights]
+    arrs, fmt = _same_type(list(lefts) + ([] if rights is None or interleaved else list(rights)))
+    L = arrs[:n]
+    R = L if len(arrs) == n else arrs[n:]
+    if interleaved:
+        fmt |= PCM_INTERLEAVED
     H = (ctypes.c_void_p * n)(*[e._h for e in encoders])
     lp = (ctypes.c_void_p * n)(*[a.ctypes.data for a in L])
     rp = (ctypes.c_void_p * n)(*[a.ctypes.data for a in R])
-    ns = (ctypes.c_size_t * n)(*[len(a) for a in L])
-    caps = [lib.lhip_max_output_bytes(e._h, len(a)) for e, a in zip(encoders, L)]
+    counts = [len(a) // e.channels if interleaved else len(a) for e, a in zip(encoders, L)]
+    ns = (ctypes.c_size_t * n)(*counts)
+    caps = [lib.lhip_max_output_bytes(e._h, c) for e, c in zip(encoders, counts)]
     outs = [np.empty(c, dtype=np.uint8) for c in caps]
     op = (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs])
     cp = (ctypes.c_size_t * n)(*caps)
     wr = (ctypes.c_int64 * n)()
-    rc = lib.lhip_encode_batch(H, n, lp, rp, ns, op, cp, wr)
+    if fmt == PCM_S16:
+        rc = lib.lhip_encode_batch(H, n, lp, rp, ns, op, cp, wr)
+    else:
+        rc = lib.lhip_encode_batch_pcm(H, n, fmt, lp, rp, ns, op, cp, wr)
     if rc != 0:
-        raise LhipError(f"lhip_encode_batch failed ({rc}): {lib.lhip_last_error().decode()}")
+        raise LhipError(f"{'lhip_encode_batch' if fmt == PCM_S16 else 'lhip_encode_batch_pcm'} failed ({rc}): {lib.lhip_last_error().decode()}")
     res = [outs[i][: wr[i]].tobytes() for i in range(n)]
     if flush:
         caps2 = [lib.lhip_max_output_bytes(e._h, 4 * 1152) for e in encoders]

@@ -7,6 +7,7 @@
 //                  (1136-1149), block types decided by kb_scan.
 // Every store into the 32-slot row / xr rounds to f32 exactly where the reference does.
 #pragma once
+#include <type_traits>
 #include "lhip_defs.h"
 #include "lhip_wave.h"
 #include "lhip_layout.h"
@@ -164,6 +165,34 @@ template <int ROW> LHIP_DEV void poly_slot(const Tables& T, const float* xt, flo
     }
     for (int i = 0; i < 32; i++) out[i] = a[i];
 }
+// kb_poly_run's staging where everything staged is new input, per sample format (F32: Float32 / Int16; UNIT: stride 1 known at compile time --
+// <0, 1> is the Int16 planar loop as it always was).  Eight loads in flight per lane: with one load per trip (the trip count is not a
+// compile-time constant) the wave waited out a full memory latency 36 times, which was most of this kernel's time
+template <int F32, int UNIT>
+LHIP_DEV void poly_stage_new(const PcmSrc& P, int first, int lo, int n_need, int lane, float* xs) {
+    typedef typename std::conditional<F32 != 0, float, int16_t>::type elem_t;
+    const int str = UNIT ? 1 : P.stride;
+    const elem_t* src = (const elem_t*)P.src + (int64_t)first * str;
+    enum { STG = 8 };
+    for (int n0 = 0; n0 < n_need; n0 += LHIP_NL * STG) {
+        typename std::conditional<F32 != 0, float, int>::type raw[STG];
+#pragma unroll
+        for (int k = 0; k < STG; k++) {                  // unconditional loads from a clamped index: a predicated load is waited for inside its branch
+            const int n = n0 + lane + LHIP_NL * k;
+            raw[k] = src[(n < lo ? lo : (n < n_need ? n : n_need - 1)) * str];
+        }
+#pragma unroll
+        for (int k = 0; k < STG; k++) LHIP_PIN_LOADED(raw[k]);
+#pragma unroll
+        for (int k = 0; k < STG; k++) {
+            const int n = n0 + lane + LHIP_NL * k;
+            float v = F32 ? pcm_f32_clean((float)raw[k]) : (float)raw[k];
+            if (P.do_scale) v = (float)((double)v * P.scale);
+            if (n < lo) v = 0.f;                            // (0 * scale could be -0 or NaN for an odd scale; the slot is defined as +0)
+            if (n < n_need) xs[(n & 31) * POLY_ROW + (n >> 5)] = v;
+        }
+    }
+}
 // `cnt` (<= POLY_PER_WAVE) consecutive granule slots gs, gs + 1, ... of ONE stream, channel ch: one transposed staging serves them all
 LHIP_DEV void kb_poly_run(const Tables& T, const Workspace& W, const StreamDesc* SD, const StreamIO* IO, int gs, int ch, int cnt, int lane, PolyLds& L) {
     const int C = T.channels_out;
@@ -176,29 +205,10 @@ LHIP_DEV void kb_poly_run(const Tables& T, const Workspace& W, const StreamDesc*
     const int s0 = 576 * q + 286 - POLY_BIAS;                 // segment index of staging slot 0 (slots below `lo` lie before the segment)
     const int n_need = POLY_N1 + 576 * (cnt - 1);
     wave_sync();
-    if (!P.plane && s0 + lo >= P.mf) {                        // wave-uniform usual case: everything staged is new Int16 input
-        // eight loads in flight per lane: with one load per trip (the trip count is not a compile-time constant) the wave waited
-        // out a full memory latency 36 times, which was most of this kernel's time
-        const int16_t* src = P.src + (s0 - P.mf);
-        enum { STG = 8 };
-        for (int n0 = 0; n0 < n_need; n0 += LHIP_NL * STG) {
-            int raw[STG];
-#pragma unroll
-            for (int k = 0; k < STG; k++) {                  // unconditional loads from a clamped index: a predicated load is waited for inside its branch
-                const int n = n0 + lane + LHIP_NL * k;
-                raw[k] = (int)src[n < lo ? lo : (n < n_need ? n : n_need - 1)];
-            }
-#pragma unroll
-            for (int k = 0; k < STG; k++) LHIP_PIN_LOADED(raw[k]);
-#pragma unroll
-            for (int k = 0; k < STG; k++) {
-                const int n = n0 + lane + LHIP_NL * k;
-                float v = (float)raw[k];
-                if (P.do_scale) v = (float)((double)v * P.scale);
-                if (n < lo) v = 0.f;                            // (0 * scale could be -0 or NaN for an odd scale; the slot is defined as +0)
-                if (n < n_need) L.xs[(n & 31) * POLY_ROW + (n >> 5)] = v;
-            }
-        }
+    if (!P.plane && s0 + lo >= P.mf) {                        // wave-uniform usual case: everything staged is new input
+        if (!P.f32 && P.stride == 1) poly_stage_new<0, 1>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+        else if (!P.f32) poly_stage_new<0, 0>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+        else poly_stage_new<1, 0>(P, s0 - P.mf, lo, n_need, lane, L.xs);
     } else {
         for (int n = lane; n < n_need; n += LHIP_NL) L.xs[(n & 31) * POLY_ROW + (n >> 5)] = (n >= lo) ? pcm_at(P, s0 + n) : 0.f;
     }

@@ -8,6 +8,7 @@
 // Behaviour follows reference PsyModel.js:1000-1383 (L3psycho_anal_ns), FFT.js:31-224 and
 // Encoder.js:166-243 (adjust_ATH); line references are given at each step.
 #pragma once
+#include <type_traits>
 #include "lhip_defs.h"
 #include "lhip_wave.h"
 #include "lhip_math.h"
@@ -162,6 +163,20 @@ template <int K> LHIP_DEV int guarded_f32_of_sum(const double (&p)[K], double sc
 #endif
 }
 
+// kb_psyA's staging of a window that lies wholly in the call's new samples, per sample format (F32: Float32 / Int16; UNIT: stride 1 known
+// at compile time -- <0, 1> is the Int16 planar loop as it always was)
+template <int F32, int UNIT>
+LHIP_DEV void psya_stage_new(const PcmSrc& P, int first, int lane, float* fz) {
+    typedef typename std::conditional<F32 != 0, float, int16_t>::type elem_t;
+    const int str = UNIT ? 1 : P.stride;
+    const elem_t* src = (const elem_t*)P.src + (int64_t)first * str;
+    for (int i = lane; i < BLKSIZE; i += LHIP_NL) {
+        float v = F32 ? pcm_f32_clean((float)src[i * str]) : (float)src[i * str];
+        if (P.do_scale) v = (float)((double)v * P.scale);
+        fz[i] = v;
+    }
+}
+
 // one wave per (granule slot >= 1 of a stream, psy channel).  ch = 0, 1: L, R.  Joint stereo adds ch = 2, 3 (mid, side) in a second
 // launch: their high-passed samples and their spectra are linear combinations of the L / R ones (PsyModel.js:1113-1121, 258-273),
 // which the L / R waves leave in W.hpf / W.fht; everything from the energies on is the same code for all four.
@@ -184,12 +199,9 @@ LHIP_DEV void kb_psyA(const Tables& T, const Workspace& W, const StreamDesc* SD,
         const int b0 = 576 * q + 304;
         if (!P.plane && b0 >= P.mf) {
             // the usual case, wave-uniform: the whole window lies in this call's new samples -- no per-sample decisions
-            const int16_t* src = P.src + (b0 - P.mf);
-            for (int i = lane; i < BLKSIZE; i += LHIP_NL) {
-                float v = (float)src[i];
-                if (P.do_scale) v = (float)((double)v * P.scale);
-                L.fz[i] = v;
-            }
+            if (!P.f32 && P.stride == 1) psya_stage_new<0, 1>(P, b0 - P.mf, lane, L.fz);
+            else if (!P.f32) psya_stage_new<0, 0>(P, b0 - P.mf, lane, L.fz);
+            else psya_stage_new<1, 0>(P, b0 - P.mf, lane, L.fz);
         } else {
             for (int i = lane; i < BLKSIZE; i += LHIP_NL) L.fz[i] = pcm_at(P, b0 + i);
         }

@@ -45,6 +45,8 @@ enum { FRAME_PROF_BASE = 64 + 2 * 8192 };      /* u64 index of g_frame's stage s
 enum { PROF_BYTES = 512 };
 #endif
 struct Context;
+static thread_local Context* g_rej_pending = nullptr;       // the last batch counted rejected Float32 samples on the device (lhip_last_batch_rejected_samples fetches the count)
+static thread_local int64_t g_rejected = 0;
 static thread_local Context* g_stat_pending = nullptr;      // the last batch was enqueued without synchronisation: its repair statistics are still on the device
 static void set_err(const std::string& e) { g_err = e; }
 
@@ -146,7 +148,8 @@ LHIP_DEV void kb_load(const Tables& T, const Workspace& W, const StreamDesc* SD,
 //     out[m] = sum_{i=0..32} x[m*r + i - 16] * blackfilt[1][i]        (x[<0] = 0; f64 accumulation in tap order)
 // and emits out[m] as soon as m*r + 16 < (samples received so far).  `p0` is the position of tap 0 of this call's
 // first output relative to this call's first input sample; positions < 0 are the carried tail of earlier calls.
-LHIP_DEV void kb_resample_elem(const Tables& T, float* dst, const int16_t* src, const float* old, int p0, int64_t t) {
+template <int F32>
+LHIP_DEV void kb_resample_elem(const Tables& T, float* dst, const void* src, int stride, const float* old, int p0, int64_t t) {
     const float* coef = T.rs_blackfilt + T.rs_bpc * RS_TAPS;
     const int64_t p = (int64_t)p0 + t * T.rs_ratio;
     const bool do_scale = !(T.scale == 0.0) && !(T.scale == 1.0);
@@ -155,7 +158,7 @@ LHIP_DEV void kb_resample_elem(const Tables& T, float* dst, const int16_t* src, 
         const int64_t q = p + i;
         float y;
         if (q < 0) y = old[(RS_TAPS - 1) + q];
-        else { y = (float)src[q]; if (do_scale) y = (float)((double)y * T.scale); }
+        else { y = pcm_new(src, F32, stride, q); if (do_scale) y = (float)((double)y * T.scale); }
         xvalue += (double)y * (double)coef[i];
     }
     dst[t] = (float)xvalue;
@@ -167,7 +170,8 @@ LHIP_DEV void kb_resample_elem(const Tables& T, float* dst, const int16_t* src, 
 // tap i reads input trunc(i + j - 15.5): truncation toward zero (the reference's `0 | ...`), so input 0 is read twice where i + j - 15.5 is
 // -0.5 and +0.5.  That is why call boundaries show in the bytes and such a stream is a call-sequence stream.  The host only asks for outputs
 // whose taps lie inside the call (j + 15.5 < n_in, at most 31 samples back into the carried tail); the clamps keep a wrong record in bounds.
-LHIP_DEV void kb_resample_frac_elem(const Tables& T, float* dst, const int16_t* src, const float* old, double itime, int n_in, int64_t k) {
+template <int F32>
+LHIP_DEV void kb_resample_frac_elem(const Tables& T, float* dst, const void* src, int stride, const float* old, double itime, int n_in, int64_t k) {
     enum { BLACKSIZE = RS_TAPS - 1 };
     const int bpc = T.rs_bpc;
     const double time0 = (double)k * T.resample_ratio;
@@ -182,7 +186,7 @@ LHIP_DEV void kb_resample_frac_elem(const Tables& T, float* dst, const int16_t* 
         const int j2 = (int)(i + j - 15.5);
         float y = 0.f;
         if (j2 < 0) { if (j2 >= -BLACKSIZE) y = old[BLACKSIZE + j2]; }
-        else if (j2 < n_in) { y = (float)src[j2]; if (do_scale) y = (float)((double)y * T.scale); }
+        else if (j2 < n_in) { y = pcm_new(src, F32, stride, j2); if (do_scale) y = (float)((double)y * T.scale); }
         xvalue += (double)y * (double)coef[i];
     }
     dst[k] = (float)xvalue;
@@ -196,12 +200,37 @@ LHIP_DEV void kb_prep_stream(const Tables& T, const Workspace& W, const StreamDe
     const int64_t off = SD[st].pcm_off + io.mf_size;
     for (int ch = 0; ch < C; ch++) {
         float* dst = W.pcm + (int64_t)ch * W.pcm_plane + off;
-        if (T.rs_frac) for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_frac_elem(T, dst, (ch ? io.src[1] : io.src[0]), io.state->rs_old[ch], io.rs_itime, io.n_in, i);
-        else for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_elem(T, dst, (ch ? io.src[1] : io.src[0]), io.state->rs_old[ch], io.rs_p0, i);
+        const void* src = ch ? io.src[1] : io.src[0];
+        const float* old = io.state->rs_old[ch];
+        if (io.f32) {                                            // the sample type is decided outside the tap loops
+            if (T.rs_frac) for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_frac_elem<1>(T, dst, src, io.stride, old, io.rs_itime, io.n_in, i);
+            else for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_elem<1>(T, dst, src, io.stride, old, io.rs_p0, i);
+        } else {
+            if (T.rs_frac) for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_frac_elem<0>(T, dst, src, io.stride, old, io.rs_itime, io.n_in, i);
+            else for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_elem<0>(T, dst, src, io.stride, old, io.rs_p0, i);
+        }
     }
 }
 LHIP_DEV void kb_prep(const Tables& T, const Workspace& W, const StreamDesc* SD, const StreamIO* IO, int nstreams, int64_t tid, int64_t nthreads) {
     for (int st = 0; st < nstreams; st++) kb_prep_stream(T, W, SD, IO, st, tid, nthreads);
+}
+
+// Float32 input by device pointer (lhip_encode_batch_device_pcm): the host cannot see the values, the read sites read a sample outside the
+// contract as +0 (pcm_f32_clean) -- this counts them, once per (stream, channel, sample) the caller handed over, for lhip_last_batch_rejected_samples.  A pass of its own
+// over the call's input (4.6 KB per two-channel frame), launched for such calls only: the read sites stay free of atomics, and several of them
+// read a sample more than once.
+LHIP_DEV unsigned long long kb_count_rejected(const StreamIO* IO, int nstreams, int C, int64_t tid, int64_t nthreads) {
+    unsigned long long bad = 0;
+    for (int st = 0; st < nstreams; st++) {
+        const StreamIO io = IO[st];
+        if (!io.f32) continue;
+        for (int ch = 0; ch < C; ch++) {
+            if (ch && io.src[1] == io.src[0]) continue;          // right == left (or no right plane): the samples exist once, as for the host entries' scan
+            const float* src = (const float*)(ch ? io.src[1] : io.src[0]);
+            for (int64_t i = tid; i < io.n_in; i += nthreads) { const float v = src[i * io.stride]; bad += !((v < 0 ? -v : v) <= PCM_F32_LIMIT); }
+        }
+    }
+    return bad;
 }
 
 LHIP_DEV void kb_save(const Tables& T, const Workspace& W, const StreamDesc* SD, const StreamIO* IO, int st, int lane, int part = 0, int nparts = 1) {
@@ -268,7 +297,7 @@ LHIP_DEV void kb_save(const Tables& T, const Workspace& W, const StreamDesc* SD,
                 if (i < RS_TAPS - 1) {
                     const int64_t q = (int64_t)io.n_in - (RS_TAPS - 1) + i;
                     if (q < 0) v = S->rs_old[ch][(RS_TAPS - 1) + q];
-                    else { v = (float)(ch ? io.src[1] : io.src[0])[q]; if (do_scale) v = (float)((double)v * T.scale); }
+                    else { v = pcm_new(ch ? io.src[1] : io.src[0], io.f32, io.stride, q); if (do_scale) v = (float)((double)v * T.scale); }
                 }
                 wave_sync();
                 if (i < RS_TAPS - 1) S->rs_old[ch][i] = v;
@@ -581,6 +610,10 @@ __global__ __launch_bounds__(64 * WPB) void g_psyA(Tables T, Workspace W, const 
 __global__ __launch_bounds__(256) void g_prep(Tables T, Workspace W, const StreamDesc* SD, const StreamIO* IO, int nstreams) {
     kb_prep(T, W, SD, IO, nstreams, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
+__global__ __launch_bounds__(256) void g_count_rejected(const StreamIO* IO, int nstreams, int C, unsigned long long* ctr) {
+    const unsigned long long bad = kb_count_rejected(IO, nstreams, C, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    if (bad) atomicAdd(ctr, bad);
+}
 __global__ __launch_bounds__(64) void g_scan_raw(Tables T, Workspace W, const StreamDesc* SD, int ngs) { const int g = blockIdx.x * 64 + threadIdx.x; if (g < ngs) kb_scan_raw(T, W, SD, g); }
 __global__ __launch_bounds__(64) void g_scan_attack(Tables T, Workspace W, const StreamDesc* SD, int ngs) { const int g = blockIdx.x * 64 + threadIdx.x; if (g < ngs) kb_scan_attack(T, W, SD, g); }
 __global__ __launch_bounds__(64) void g_scan_blocktype(Tables T, Workspace W, const StreamDesc* SD, int ngs) { const int g = blockIdx.x * 64 + threadIdx.x; if (g < ngs) kb_scan_blocktype(T, W, SD, g); }
@@ -878,8 +911,8 @@ template <int RESV> __global__ __launch_bounds__(64 * FR_WAVES) void g_frame(QAr
 #endif
 }
 // optional per-kernel timing with HIP events on the launch stream (bench.py roofline accounting)
-enum { KT_LOAD, KT_PREP, KT_PSYA, KT_SCAN, KT_PSYB, KT_POLY, KT_MDCT, KT_QUANT, KT_VALIDATE, KT_REPAIR, KT_BITS, KT_SAVE, KT_N };
-static const char* const g_kt_names[KT_N] = {"load", "prep", "psyA", "scan", "psyB", "polyphase", "mdct", "quant", "validate", "repair", "bits", "save"};
+enum { KT_LOAD, KT_PREP, KT_PSYA, KT_SCAN, KT_PSYB, KT_POLY, KT_MDCT, KT_QUANT, KT_VALIDATE, KT_REPAIR, KT_BITS, KT_SAVE, KT_COUNT, KT_N };
+static const char* const g_kt_names[KT_N] = {"load", "prep", "psyA", "scan", "psyB", "polyphase", "mdct", "quant", "validate", "repair", "bits", "save", "count_rejected"};
 // The switch is process-wide (bench.py turns it on for one extra, untimed step); the events of a batch belong to the calling
 // thread (a batch runs entirely inside one run_batch call), the accumulators are shared by all devices and guarded by g_kt_mu.
 static std::atomic<bool> g_kt_on{false};
@@ -1252,7 +1285,7 @@ struct PinBuf {
 // slower than one batch at a time in every form, profiles/r04_pass5_ab_*.txt, and removed it: DESIGN.md, measured and discarded.)
 struct WorkSet {
     DevBuf pcm, peaks, loud, eb_l, mask_idx, eb_s, ecb_s, att_raw, uselong, ul_tmp, last_attack, tent, prev_short, blocktype,
-        ath_adjust, ath_limit, E, sb, xr, side, l3, seed, seed_flag, nflagged, slow_list, frame_bytes, desc, in16, out8, prof, fht, hpf, tot_ener, reval, att_clean, nb1, nb2, fr, out_bytes, vdig, small;
+        ath_adjust, ath_limit, E, sb, xr, side, l3, seed, seed_flag, nflagged, slow_list, frame_bytes, desc, in16, rejected, out8, prof, fht, hpf, tot_ener, reval, att_clean, nb1, nb2, fr, out_bytes, vdig, small;
     PinBuf pin_in, pin_out;     // small host-buffer calls (run_batch): everything that travels in / out, staged once in pinned memory
     // last batch (for debug taps)
     Workspace lastW; int lastC = 0, lastCp = 0; bool have_last = false;
@@ -1320,13 +1353,18 @@ struct lhip_stream {
 // batch encode
 // ===========================================================================================
 struct Job {
-    lhip_stream* s; const int16_t* l; const int16_t* r; size_t n; uint8_t* out; size_t cap; int64_t written;
+    lhip_stream* s; const void* l; const void* r; size_t n; uint8_t* out; size_t cap; int64_t written;
     int F; int64_t bytes;
     int64_t n_out;              // samples this call appends to the encoder's buffer (== n unless resampling)
     bool flush = false;         // bit reservoir: the stream ends with this call (its bitstream is padded to the end of the last frame)
     double rs_len = -1;         // non-integer ratio, flush only: the reference's (possibly fractional) length of this bunch of zeros; n = ceil(rs_len)
     double rs_used = 0;         // non-integer ratio: num_used of the pass (== the call's length for every call that is accepted; a flush pass may end on a whole frame)
+    int f32 = 0, inter = 0;     // sample format of l / r: Float32 (else Int16); interleaved (l holds channels * n samples, r is ignored)
+    bool count_rejected = false;   // Float32 by device pointer from the caller: count the samples the read sites refuse
 };
+// bytes per sample / the four formats of the C ABI
+static inline size_t fmt_bps(int f32) { return f32 ? 4 : 2; }
+static inline bool fmt_ok(int format) { return format >= 0 && format <= 3; }
 
 // resampling by the integer ratio r: output sample m exists once m*r + 16 < (input samples received) -- see kb_resample_elem
 static int64_t rs_outputs(int64_t n_in_total, int r) { return n_in_total > 16 ? (n_in_total - 16 + r - 1) / r : 0; }
@@ -1411,6 +1449,8 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     std::vector<StreamIO> io(S);
     int nfs = 0, ngs = 0, nfr = 0, maxF = 0;
     int64_t pcm_plane = 0, in_total = 0, out_total = 0;
+    size_t in_bytes = 0;                           // host input as it travels: every job's samples in its format, jobs 4-byte aligned
+    bool count_rej = false;
     for (int i = 0; i < S; i++) {
         Job& j = jobs[i];
         lhip_stream* s = j.s;
@@ -1439,6 +1479,8 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
         if (j.F > maxF) maxF = j.F;
         pcm_plane += (total + 63) & ~(int64_t)63;
         in_total += (int64_t)j.n; out_total += (j.bytes + 15) & ~(int64_t)15;
+        in_bytes += (j.n * (size_t)C * fmt_bps(j.f32) + 3) & ~(size_t)3;
+        count_rej |= j.count_rejected && j.f32 && j.n > 0;
     }
     // ---- workspace ----
     Workspace W;
@@ -1468,7 +1510,6 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     auto a16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t desc_sd = 0, desc_io = a16(desc_sd + (size_t)S * sizeof(StreamDesc)), desc_fm = a16(desc_io + (size_t)S * sizeof(StreamIO)),
                  desc_gm = a16(desc_fm + (size_t)nfs * 4), desc_bytes = desc_gm + (size_t)ngs * 4;
-    const size_t in_bytes = (size_t)in_total * 2 * C;
     const size_t sm_out = 0, sm_nfl = a16((size_t)out_total + 64), sm_ob = sm_nfl + 256, sm_sf = a16(sm_ob + (size_t)S * 4 + 64), sm_rv = sm_sf + a16(FR * 4),
                  sm_desc = sm_rv + a16(FR * 4), sm_in = a16(sm_desc + desc_bytes), sm_end = sm_in + in_bytes + 64;
     static const bool no_small = []() { const char* e = getenv("LAMEJS_HIP_NO_SMALL_CALLS"); return e && e[0] == '1'; }();
@@ -1499,7 +1540,7 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     // ---- descriptors / inputs ----
     std::vector<int32_t> fmap(nfs), gmap(ngs);
     std::vector<int64_t> out_rel(S);              // a stream's output offset inside the output area (sd.out_off becomes the absolute address below)
-    int64_t in_off = 0;
+    size_t in_off = 0;                            // bytes
     uint8_t* const pin = small ? (uint8_t*)ws.pin_in.p : nullptr;       // mirrors the device block from sm_nfl on
     if (small) memset(pin, 0, sm_desc - sm_nfl);                       // the counters start from zero
     for (int i = 0; i < S; i++) {
@@ -1511,21 +1552,27 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
         o.rs_p0 = T.rs_ratio <= 1 ? 0 : (int)(rs_outputs(j.s->rs_n_in, T.rs_ratio) * T.rs_ratio - 16 - j.s->rs_n_in);
         o.rs_itime = j.s->rs_itime;
         out_rel[i] = sd[i].out_off;
+        const size_t bps = fmt_bps(j.f32);
+        const bool il = j.inter && C == 2;            // (one channel: interleaved is planar)
+        o.f32 = j.f32 ? 1 : 0; o.stride = il ? 2 : 1;
         if (dev_io) {
-            o.src[0] = j.l; o.src[1] = (C == 2 && j.r) ? j.r : j.l; o.out = j.out;
+            o.src[0] = j.l; o.src[1] = il ? (const void*)((const uint8_t*)j.l + bps) : ((C == 2 && j.r) ? j.r : j.l); o.out = j.out;
         } else {
-            int16_t* base = small ? (int16_t*)(smb + sm_in) : (int16_t*)ws.in16.p;
-            int16_t* hbase = small ? (int16_t*)(pin + (sm_in - sm_nfl)) : nullptr;
+            uint8_t* base = small ? smb + sm_in : (uint8_t*)ws.in16.p;
+            uint8_t* hbase = small ? pin + (sm_in - sm_nfl) : nullptr;
+            const size_t plane = j.n * bps * (il ? 2 : 1);          // an interleaved call is ONE copy
             o.src[0] = base + in_off;
-            if (small) memcpy(hbase + in_off, j.l, j.n * 2);
-            else if (!rt::h2d((void*)o.src[0], j.l, j.n * 2, st)) return false;
-            in_off += (int64_t)j.n;
-            if (C == 2) {
+            if (small) memcpy(hbase + in_off, j.l, plane);
+            else if (!rt::h2d((void*)o.src[0], j.l, plane, st)) return false;
+            if (il) o.src[1] = base + in_off + bps;
+            in_off += plane;
+            if (C == 2 && !il) {
                 o.src[1] = base + in_off;
-                if (small) memcpy(hbase + in_off, j.r ? j.r : j.l, j.n * 2);
-                else if (!rt::h2d((void*)o.src[1], j.r ? j.r : j.l, j.n * 2, st)) return false;
-                in_off += (int64_t)j.n;
-            } else o.src[1] = o.src[0];
+                if (small) memcpy(hbase + in_off, j.r ? j.r : j.l, plane);
+                else if (!rt::h2d((void*)o.src[1], j.r ? j.r : j.l, plane, st)) return false;
+                in_off += plane;
+            } else if (!il) o.src[1] = o.src[0];
+            in_off = (in_off + 3) & ~(size_t)3;
             o.out = (small ? smb + sm_out : (uint8_t*)ws.out8.p) + sd[i].out_off;
         }
     }
@@ -1564,6 +1611,19 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     W.io = dIO;
     CALL_STAMP(1);                                  // input copies, descriptors, counters zeroed: enqueued
 
+    g_rejected = 0; g_rej_pending = nullptr;
+    if (count_rej) {
+#ifdef LHIP_HOSTSIM
+        g_rejected = (int64_t)kb_count_rejected(dIO, S, C, 0, 1);
+#else
+        if (!ws.rejected.ensure(64) || !rt::dzero(ws.rejected.p, 8, st)) return false;
+        int64_t nb = (in_total + 255) / 256;
+        if (nb > 2048) nb = 2048;
+        if (nb < 1) nb = 1;
+        LAUNCHB(KT_COUNT, g_count_rejected, (int)nb, 256, st, dIO, S, C, (unsigned long long*)ws.rejected.p);
+        g_rej_pending = ctx;
+#endif
+    }
     int64_t repaired = 0, iters = 0;
     // at most one frame per stream: the whole frame program in one launch (kb_frame_stage); LAMEJS_HIP_NO_FRAME_KERNEL=1 keeps the separate kernels
     static const bool no_frame = []() { const char* e = getenv("LAMEJS_HIP_NO_FRAME_KERNEL"); return e && e[0] == '1'; }();
@@ -2035,7 +2095,7 @@ int lhip_output_bytes_is_exact(const lhip_stream* s) {
     return s->ts->T.disable_reservoir ? 1 : 0;
 }
 
-static int encode_many(lhip_stream* const* streams, size_t n, const int16_t* const* l, const int16_t* const* r,
+static int encode_many(lhip_stream* const* streams, size_t n, int format, const void* const* l, const void* const* r,
                        const size_t* ns, uint8_t* const* out, const size_t* cap, int64_t* written, bool dev_io, bool sync, bool flush_stream = false) {
     if (n == 0) return 0;
     std::vector<Job> jobs(n);
@@ -2043,6 +2103,8 @@ static int encode_many(lhip_stream* const* streams, size_t n, const int16_t* con
         if (!streams[i] || streams[i]->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
         if (streams[i]->ctx != streams[0]->ctx) { set_err("batch: streams on different devices"); return LHIP_ERR_INTERNAL; }
         jobs[i] = Job{streams[i], l[i], r ? r[i] : nullptr, ns[i], out[i], cap[i], 0, 0, 0, 0};
+        jobs[i].f32 = format & LHIP_PCM_F32; jobs[i].inter = (format & LHIP_PCM_INTERLEAVED) != 0;
+        jobs[i].count_rejected = dev_io && jobs[i].f32;
     }
     // Bit reservoir (extension): the frames of a stream are a serial chain, walked by one workgroup per stream inside the launch
     // (g_resv_stream); a stream that ends with this call (flush) has its bitstream padded by the same launch -- decided per stream
@@ -2128,13 +2190,13 @@ static int call_frames(const lhip_stream* s, size_t nsamples) {
     return total >= mf_needed ? (int)((total - mf_needed) / frame) + 1 : 0;
 }
 // One piece of host input for one stream: `n` samples per channel from l / r; its frames' bytes go to the stream's destination (running).
-struct HostPiece { int si; const int16_t* l; const int16_t* r; size_t n; };
+struct HostPiece { int si; const void* l; const void* r; size_t n; };
 // The overlapped host path, in general form: `units` are processed in order, each a batch of pieces (one per stream at most) -- unit k + 1
 // travels to the device (copy stream) while unit k is encoded (launch stream) and the bytes of unit k - 1 travel back.  For ONE long stream
 // the units are consecutive sample ranges of its input (encode_host_chunked); for MANY streams (lhip_encode_batch with host buffers,
 // BASELINE configs[4] through the JavaScript encodeBatch) they are groups of streams.  dst[si] / cap[si]: stream si's output buffer;
 // written[si] receives its byte count.  A failed call gives every stream back as it found it.
-static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& strs, const std::vector<std::vector<HostPiece>>& units,
+static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& strs, const std::vector<std::vector<HostPiece>>& units, int format,
                                  uint8_t* const* dst, int64_t* written) {
     std::lock_guard<std::mutex> chunk_lk(ctx->chunk_mu);
     const size_t NS = strs.size();
@@ -2151,6 +2213,9 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
         if (o > out_max) out_max = o;
     }
     const size_t stride = in_max, out_chunk = out_max + 64;
+    const int f32 = format & LHIP_PCM_F32;
+    const size_t bps = fmt_bps(f32);
+    const bool il = (format & LHIP_PCM_INTERLEAVED) && C == 2;
     // what a failed call must give back: the host-side counters and the device-side state record of every stream (a call that fails in unit
     // k > 0 would otherwise leave streams k units further on with `out` half written -- "a failed call consumes nothing" has to hold here too)
     struct Snap { int mf, ste, lag; int64_t fn, rs; };
@@ -2165,7 +2230,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
             for (int i = 0; i < 4; i++) if (!rt::event_create(&e[i])) return LHIP_ERR_INTERNAL;
             ctx->ev_in[0] = e[0]; ctx->ev_in[1] = e[1]; ctx->ev_done[0] = e[2]; ctx->ev_done[1] = e[3]; ctx->copy_stream = cs;
         }
-        if (!ctx->chunk_in.ensure(2 * C * stride * 2 + 64) || !ctx->chunk_out.ensure(2 * out_chunk) || !ctx->chunk_fx.ensure(units.size() * 16 + 16) ||
+        if (!ctx->chunk_in.ensure(2 * C * stride * bps + 64) || !ctx->chunk_out.ensure(2 * out_chunk) || !ctx->chunk_fx.ensure(units.size() * 16 + 16) ||
             !ctx->state_bak.ensure(NS * sizeof(StreamState))) return LHIP_ERR_INTERNAL;
         for (size_t i = 0; i < NS; i++)
             if (!rt::d2d((uint8_t*)ctx->state_bak.p + i * sizeof(StreamState), strs[i]->d_state, sizeof(StreamState), ctx->stream)) return LHIP_ERR_INTERNAL;
@@ -2202,7 +2267,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
         const int par = (int)(k & 1);
         const std::vector<HostPiece>& u = units[k];
         const double t_a = trace_chunks ? ms_now() : 0.0;
-        int16_t* d_in = (int16_t*)ctx->chunk_in.p + (size_t)par * C * stride;
+        uint8_t* d_in = (uint8_t*)ctx->chunk_in.p + (size_t)par * C * stride * bps;
         uint8_t* d_out = (uint8_t*)ctx->chunk_out.p + (size_t)par * out_chunk;
         // buffer `par` was last used by unit k - 2: its kernels are done (drain() waited for them before unit k - 1 was enqueued)
         // (copies straight from the caller's pageable memory: measured as fast as copies through pinned staging filled by four host
@@ -2211,10 +2276,17 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
         size_t io = 0, oo = 0;
         for (size_t j = 0; j < u.size(); j++) {
             const HostPiece& pc = u[j];
-            if (!rt::h2d(d_in + io, pc.l, pc.n * 2, cs)) return fail(nullptr);
-            if (C == 2 && !rt::h2d(d_in + stride + io, pc.r ? pc.r : pc.l, pc.n * 2, cs)) return fail(nullptr);
             const size_t ocap = ((pc.n / spf + 3) * obytes + 63) & ~(size_t)63;
-            jobs[j] = Job{strs[pc.si], d_in + io, C == 2 ? d_in + stride + io : nullptr, pc.n, d_out + oo, ocap, 0, 0, 0, 0};
+            if (il) {                                      // interleaved two-channel input: one copy, read with stride 2
+                if (!rt::h2d(d_in + 2 * io * bps, pc.l, 2 * pc.n * bps, cs)) return fail(nullptr);
+                jobs[j] = Job{strs[pc.si], d_in + 2 * io * bps, nullptr, pc.n, d_out + oo, ocap, 0, 0, 0, 0};
+                jobs[j].inter = 1;
+            } else {
+                if (!rt::h2d(d_in + io * bps, pc.l, pc.n * bps, cs)) return fail(nullptr);
+                if (C == 2 && !rt::h2d(d_in + (stride + io) * bps, pc.r ? pc.r : pc.l, pc.n * bps, cs)) return fail(nullptr);
+                jobs[j] = Job{strs[pc.si], d_in + io * bps, C == 2 ? d_in + (stride + io) * bps : nullptr, pc.n, d_out + oo, ocap, 0, 0, 0, 0};
+            }
+            jobs[j].f32 = f32;
             io += (pc.n + 63) & ~(size_t)63; oo += ocap;
         }
         if (!rt::event_record(ctx->ev_in[par], cs) || !rt::stream_wait_event(ks, ctx->ev_in[par])) return fail(nullptr);
@@ -2258,7 +2330,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
 }
 
 // ONE long stream: consecutive sample ranges of the call (chunk schedule above)
-static int64_t encode_host_chunked(lhip_stream* s, const int16_t* left, const int16_t* right, size_t nsamples, uint8_t* out, size_t out_cap) {
+static int64_t encode_host_chunked(lhip_stream* s, int format, const void* left, const void* right, size_t nsamples, uint8_t* out, size_t out_cap) {
     const Tables& T = s->ts->T;
     const ChunkSchedule& cfg = host_chunk_schedule();
     const size_t mul = (!cfg.fixed && T.channels_out == 2) ? 2 : 1;
@@ -2266,25 +2338,27 @@ static int64_t encode_host_chunked(lhip_stream* s, const int16_t* left, const in
     // the whole call must fit the caller's buffer BEFORE anything is consumed (a failed call consumes nothing)
     if ((size_t)batch_bytes(*s->ts, s->slot_lag, call_frames(s, nsamples)) > out_cap) { set_err("output buffer too small"); return LHIP_ERR_BUFFER_TOO_SMALL; }
     std::vector<std::vector<HostPiece>> units;
+    const bool il = (format & LHIP_PCM_INTERLEAVED) && T.channels_out == 2;
+    const size_t step = fmt_bps(format & LHIP_PCM_F32) * (il ? 2 : 1);       // bytes from one sample position of the call to the next
     {
         const size_t cap = cfg.cap * mul * spf;
         size_t p = 0, cur = cfg.first * mul * spf;
         while (p < nsamples) {
             size_t m = nsamples - p < cur ? nsamples - p : cur;
             if (nsamples - p - m < m / 4 && nsamples - p <= cap) m = nsamples - p;     // no short chunk at the end: a launch for a few frames costs a whole tail
-            units.push_back({HostPiece{0, left + p, right ? right + p : nullptr, m}});
+            units.push_back({HostPiece{0, (const uint8_t*)left + p * step, (right && !il) ? (const uint8_t*)right + p * step : nullptr, m}});
             p += m;
             cur = cfg.growth * cur < cap ? cfg.growth * cur : cap;
         }
     }
     int64_t w = 0;
     uint8_t* d = out;
-    const int rc = encode_host_pipelined(s->ctx, {s}, units, &d, &w);
+    const int rc = encode_host_pipelined(s->ctx, {s}, units, format, &d, &w);
     return rc < 0 ? rc : w;
 }
 
 // MANY streams with host buffers (lhip_encode_batch): groups of streams as units -- a group's copies hide behind the encode of the group before
-static int encode_host_groups(lhip_stream* const* streams, size_t n, const int16_t* const* l, const int16_t* const* r, const size_t* ns,
+static int encode_host_groups(lhip_stream* const* streams, size_t n, int format, const void* const* l, const void* const* r, const size_t* ns,
                               uint8_t* const* out, const size_t* cap, int64_t* written) {
     const Tables& T = streams[0]->ts->T;
     const size_t spf = (size_t)576 * T.mode_gr * T.rs_ratio;
@@ -2305,23 +2379,52 @@ static int encode_host_groups(lhip_stream* const* streams, size_t n, const int16
     }
     std::vector<lhip_stream*> strs(streams, streams + n);
     std::vector<int64_t> w(n, 0);
-    const int rc = encode_host_pipelined(streams[0]->ctx, strs, units, out, w.data());
+    const int rc = encode_host_pipelined(streams[0]->ctx, strs, units, format, out, w.data());
     for (size_t i = 0; i < n; i++) if (written) written[i] = rc < 0 ? (int64_t)rc : w[i];
     return rc;
 }
 
-int64_t lhip_encode(lhip_stream* s, const int16_t* left, const int16_t* right, size_t nsamples, uint8_t* out, size_t out_cap) {
+// Float32 input through a host pointer: the whole call is looked at before anything is consumed.  A sample that is not finite or lies beyond
+// +-131072 refuses the call (the reference encodes NaN and infinities into garbage; here they never reach a kernel).  `count` elements.
+static bool scan_f32(const void* p, size_t count, size_t* where) {
+    const float* f = (const float*)p;
+    for (size_t i = 0; i < count; i++) if (!((f[i] < 0 ? -f[i] : f[i]) <= PCM_F32_LIMIT)) { *where = i; return false; }
+    return true;
+}
+// the host-pointer entries' check of one stream's input; on refusal lhip_last_error() names stream, channel, index and value
+static bool host_samples_ok(size_t stream_idx, int channels, int format, const void* left, const void* right, size_t n) {
+    if (!(format & LHIP_PCM_F32) || n == 0 || !left) return true;
+    const bool il = (format & LHIP_PCM_INTERLEAVED) && channels == 2;
+    size_t w = 0;
+    int ch = 0;
+    const void* bad = nullptr;
+    if (!scan_f32(left, il ? 2 * n : n, &w)) { bad = left; if (il) { ch = (int)(w & 1); } }
+    else if (!il && channels == 2 && right && right != left && !scan_f32(right, n, &w)) { bad = right; ch = 1; }
+    if (!bad) return true;
+    char txt[256];
+    snprintf(txt, sizeof txt, "Float32 sample outside the contract (finite, |x| <= 131072): stream %zu, channel %d, index %zu, value %g; nothing was consumed",
+             stream_idx, ch, il ? w / 2 : w, (double)((const float*)bad)[w]);
+    set_err(txt);
+    return false;
+}
+
+int64_t lhip_encode_pcm(lhip_stream* s, int format, const void* left, const void* right, size_t nsamples, uint8_t* out, size_t out_cap) {
     if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    if (!fmt_ok(format)) { set_err("unknown sample format"); return LHIP_ERR_INTERNAL; }
     if (nsamples == 0) return 0;
     if (!left) { set_err("null input"); return LHIP_ERR_INTERNAL; }
+    if (!host_samples_ok(0, s->ts->T.channels_out, format, left, right, nsamples)) return LHIP_ERR_INTERNAL;
     {
         static const bool no_chunk = []() { const char* e = getenv("LAMEJS_HIP_NO_HOST_CHUNKS"); return e && e[0] == '1'; }();
         const Tables& T = s->ts->T;
-        if (!no_chunk && T.disable_reservoir && !T.rs_frac && nsamples > (size_t)2 * host_chunk_schedule().first * 576 * T.mode_gr * T.rs_ratio) return encode_host_chunked(s, left, right, nsamples, out, out_cap);
+        if (!no_chunk && T.disable_reservoir && !T.rs_frac && nsamples > (size_t)2 * host_chunk_schedule().first * 576 * T.mode_gr * T.rs_ratio) return encode_host_chunked(s, format, left, right, nsamples, out, out_cap);
     }
     int64_t w = 0;
-    const int rc = encode_many(&s, 1, &left, &right, &nsamples, &out, &out_cap, &w, false, true);
+    const int rc = encode_many(&s, 1, format, &left, &right, &nsamples, &out, &out_cap, &w, false, true);
     return rc < 0 ? rc : w;
+}
+int64_t lhip_encode(lhip_stream* s, const int16_t* left, const int16_t* right, size_t nsamples, uint8_t* out, size_t out_cap) {
+    return lhip_encode_pcm(s, LHIP_PCM_S16, left, right, nsamples, out, out_cap);
 }
 
 static size_t flush_zeros(lhip_stream* s) {
@@ -2489,17 +2592,24 @@ int64_t lhip_flush(lhip_stream* s, uint8_t* out, size_t out_cap) {
     const size_t z = flush_zeros(s);
     if (z == 0) { s->mf_samples_to_encode = 0; return 0; }
     std::vector<int16_t> zeros(z, 0);
-    const int16_t* l = zeros.data();
-    const int16_t* r = zeros.data();
+    const void* l = zeros.data();
+    const void* r = zeros.data();
     int64_t w = 0;
-    const int rc = encode_many(&s, 1, &l, &r, &z, &out, &out_cap, &w, false, true, true);
+    const int rc = encode_many(&s, 1, LHIP_PCM_S16, &l, &r, &z, &out, &out_cap, &w, false, true, true);
     if (rc < 0) return rc;                 // nothing was consumed (e.g. -1: the call can be repeated with a larger buffer)
     s->mf_samples_to_encode = 0;
     return w;
 }
 
-int lhip_encode_batch(lhip_stream* const* streams, size_t nstreams, const int16_t* const* left, const int16_t* const* right,
-                      const size_t* nsamples, uint8_t* const* out, const size_t* out_cap, int64_t* written) {
+int lhip_encode_batch_pcm(lhip_stream* const* streams, size_t nstreams, int format, const void* const* left, const void* const* right,
+                          const size_t* nsamples, uint8_t* const* out, const size_t* out_cap, int64_t* written) {
+    if (!fmt_ok(format)) { set_err("unknown sample format"); return LHIP_ERR_INTERNAL; }
+    if ((format & LHIP_PCM_F32) && streams && left && nsamples)       // every stream's samples are looked at before any stream consumes anything
+        for (size_t i = 0; i < nstreams; i++)
+            if (streams[i] && streams[i]->magic == 0x4c484950 && !host_samples_ok(i, streams[i]->ts->T.channels_out, format, left[i], right ? right[i] : nullptr, nsamples[i])) {
+                for (size_t k = 0; k < nstreams; k++) if (written) written[k] = LHIP_ERR_INTERNAL;
+                return LHIP_ERR_INTERNAL;
+            }
     // many streams with a lot of input: groups of streams go through the overlapped host path (copies behind the encode of the group before)
     if (nstreams > 1 && streams && left && nsamples && out && out_cap) {
         static const bool no_chunk = []() { const char* e = getenv("LAMEJS_HIP_NO_HOST_CHUNKS"); return e && e[0] == '1'; }();
@@ -2512,15 +2622,19 @@ int lhip_encode_batch(lhip_stream* const* streams, size_t nstreams, const int16_
         }
         if (ok && streams[0]->ts->T.disable_reservoir && !streams[0]->ts->T.rs_frac) {
             const Tables& T = streams[0]->ts->T;
-            if (total > (size_t)4 * host_chunk_schedule().first * 576 * T.mode_gr * T.rs_ratio) return encode_host_groups(streams, nstreams, left, right, nsamples, out, out_cap, written);
+            if (total > (size_t)4 * host_chunk_schedule().first * 576 * T.mode_gr * T.rs_ratio) return encode_host_groups(streams, nstreams, format, left, right, nsamples, out, out_cap, written);
         }
     }
-    return encode_many(streams, nstreams, left, right, nsamples, out, out_cap, written, false, true);
+    return encode_many(streams, nstreams, format, left, right, nsamples, out, out_cap, written, false, true);
+}
+int lhip_encode_batch(lhip_stream* const* streams, size_t nstreams, const int16_t* const* left, const int16_t* const* right,
+                      const size_t* nsamples, uint8_t* const* out, const size_t* out_cap, int64_t* written) {
+    return lhip_encode_batch_pcm(streams, nstreams, LHIP_PCM_S16, (const void* const*)left, (const void* const*)right, nsamples, out, out_cap, written);
 }
 
 int lhip_flush_batch(lhip_stream* const* streams, size_t nstreams, uint8_t* const* out, const size_t* out_cap, int64_t* written) {
     std::vector<std::vector<int16_t>> zs(nstreams);
-    std::vector<const int16_t*> l(nstreams);
+    std::vector<const void*> l(nstreams);
     std::vector<size_t> ns(nstreams);
     bool any_frac = false;
     for (size_t i = 0; i < nstreams; i++) any_frac |= streams[i] && streams[i]->magic == 0x4c484950 && streams[i]->ts->T.rs_frac;
@@ -2539,14 +2653,30 @@ int lhip_flush_batch(lhip_stream* const* streams, size_t nstreams, uint8_t* cons
         zs[i].assign(ns[i] ? ns[i] : 1, 0);
         l[i] = zs[i].data();
     }
-    const int rc = encode_many(streams, nstreams, l.data(), l.data(), ns.data(), out, out_cap, written, false, true, true);
+    const int rc = encode_many(streams, nstreams, LHIP_PCM_S16, l.data(), l.data(), ns.data(), out, out_cap, written, false, true, true);
     if (rc >= 0) for (size_t i = 0; i < nstreams; i++) streams[i]->mf_samples_to_encode = 0;
     return rc;
 }
 
 int lhip_encode_batch_device(lhip_stream* const* streams, size_t nstreams, const int16_t* const* d_left, const int16_t* const* d_right,
                              const size_t* nsamples, uint8_t* const* d_out, const size_t* out_cap, int64_t* written, int sync) {
-    return encode_many(streams, nstreams, d_left, d_right, nsamples, d_out, out_cap, written, true, sync != 0);
+    return encode_many(streams, nstreams, LHIP_PCM_S16, (const void* const*)d_left, (const void* const*)d_right, nsamples, d_out, out_cap, written, true, sync != 0);
+}
+int lhip_encode_batch_device_pcm(lhip_stream* const* streams, size_t nstreams, int format, const void* const* d_left, const void* const* d_right,
+                                 const size_t* nsamples, uint8_t* const* d_out, const size_t* out_cap, int64_t* written, int sync) {
+    if (!fmt_ok(format)) { set_err("unknown sample format"); return LHIP_ERR_INTERNAL; }
+    return encode_many(streams, nstreams, format, d_left, d_right, nsamples, d_out, out_cap, written, true, sync != 0);
+}
+int64_t lhip_last_batch_rejected_samples(void) {
+    if (g_rej_pending) {                       // the count is on the device: wait for the batch and fetch it
+        Context* ctx = g_rej_pending;
+        g_rej_pending = nullptr;
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        unsigned long long v = 0;
+        if (!rt::set_device(ctx->device) || !rt::d2h(&v, ctx->ws.rejected.p, sizeof v, ctx->stream) || !rt::sync(ctx->stream)) return LHIP_ERR_INTERNAL;
+        g_rejected = (int64_t)v;
+    }
+    return g_rejected;
 }
 
 // ---- frame-range sharding of ONE stream (second mode): speculate the state at a cut, verify it, transplant on a miss ----

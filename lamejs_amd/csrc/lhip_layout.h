@@ -77,9 +77,10 @@ struct StreamState {                // psy arrays hold 4 channels: L, R and -- j
 
 struct StreamIO {          // per stream, per launch (device array parallel to StreamDesc)
     StreamState* state;
-    const int16_t* src[2]; // new samples (device addresses)
+    const void* src[2];    // new samples (device addresses): first sample of channel 0 / 1 in the call's sample format
     uint8_t* out;          // where this stream's frames go (device address)
     int32_t n_new, mf_size;    // samples appended to the encoder's buffer by this call / already buffered
+    int32_t f32, stride;       // sample format of this call: 0 Int16 / 1 Float32; elements from one sample of a channel to the next (1 planar, 2 interleaved stereo)
     int32_t n_in, rs_p0;       // resampling streams: input samples of this call; input position (relative to this call's
                                // first sample, >= -32) of tap 0 of the first new output sample
     double rs_itime;           // non-integer ratio: the resampler's clock for this call (Lame.js:1767, 1813); kept by the host, it depends on call lengths only
@@ -87,20 +88,31 @@ struct StreamIO {          // per stream, per launch (device array parallel to S
 
 // Where the samples of a stream's segment (carried tail ++ this call's new samples) come from.  Without resampling nothing is
 // materialised: a sample below `mf` is the carried tail (scaled f32, StreamState), the others are converted from the caller's
-// Int16 on the fly -- Lame.js:1554-1560 is one multiply, `(float)((double)(float)s16 * scale)` -- so the psychoacoustics and the
-// filterbank read 2 bytes per sample instead of a 4-byte copy that another kernel had to write first.  Resampling
+// samples on the fly -- Lame.js:1554-1560 is one multiply, `(float)((double)(float)s16 * scale)` -- so the psychoacoustics and the
+// filterbank read each sample where it is consumed instead of a 4-byte copy that another kernel had to write first.  Resampling
 // configurations (integer-ratio FIR in front, g_prep) read the f32 plane that kernel fills.
+// Sample format of a call (lamejs_hip.h: LHIP_PCM_*): Int16 or Float32 elements, `stride` elements apart (planar: 1; interleaved stereo:
+// 2, channel 1 starting one element after channel 0).  A Float32 sample outside the contract -- not finite, or |x| > PCM_F32_LIMIT --
+// is read as +0 at EVERY read site (pcm_f32_clean: one compare, false for NaN): nothing non-finite reaches a kernel's arithmetic.
+#define PCM_F32_LIMIT 131072.0f
+LHIP_DEV float pcm_f32_clean(float v) { return (v < 0 ? -v : v) <= PCM_F32_LIMIT ? v : 0.f; }
+// new sample i of a channel, unscaled (F32 / stride: wave-uniform)
+LHIP_DEV float pcm_new(const void* src, int f32, int stride, int64_t i) {
+    if (f32) return pcm_f32_clean(((const float*)src)[i * stride]);
+    return (float)((const int16_t*)src)[i * stride];
+}
 struct PcmSrc {
     const float* plane;      // != nullptr: materialised segment (resampling configurations)
     const float* tail;       // carried samples [0, mf)
-    const int16_t* src;      // new samples [mf, ...)
+    const void* src;         // new samples [mf, ...)
     int mf, do_scale;
+    int f32, stride;         // StreamIO::f32, StreamIO::stride
     double scale;
 };
 LHIP_DEV float pcm_at(const PcmSrc& P, int s) {
     if (P.plane) return P.plane[s];
     if (s < P.mf) return P.tail[s];
-    float v = (float)P.src[s - P.mf];
+    float v = pcm_new(P.src, P.f32, P.stride, s - P.mf);
     if (P.do_scale) v = (float)((double)v * P.scale);
     return v;
 }
@@ -179,7 +191,7 @@ LHIP_DEV int vd_step(uint32_t h) { return (int)((h >> 16) & 255u); }
 LHIP_DEV PcmSrc pcm_source(const Tables& T, const Workspace& W, const StreamDesc& sd, const StreamIO& io, int ch) {
     PcmSrc P;
     P.plane = T.rs_ratio != 1 ? W.pcm + (int64_t)ch * W.pcm_plane + sd.pcm_off : nullptr;
-    P.tail = io.state->pcm_tail[ch]; P.src = ch ? io.src[1] : io.src[0]; P.mf = io.mf_size;       // (not io.src[ch]: a dynamic index into a by-value copy of the record makes the copy a private array)
+    P.tail = io.state->pcm_tail[ch]; P.src = ch ? io.src[1] : io.src[0]; P.mf = io.mf_size; P.f32 = io.f32; P.stride = io.stride;       // (not io.src[ch]: a dynamic index into a by-value copy of the record makes the copy a private array)
     P.do_scale = !(T.scale == 0.0) && !(T.scale == 1.0); P.scale = T.scale;
     return P;
 }

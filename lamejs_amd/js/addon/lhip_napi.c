@@ -32,6 +32,8 @@ static size_t (*p_max_out)(const lhip_stream*, size_t);
 static int (*p_is_exact)(const lhip_stream*);
 static int64_t (*p_out_bytes)(const lhip_stream*, size_t);
 static int (*p_encode_batch)(lhip_stream* const*, size_t, const int16_t* const*, const int16_t* const*, const size_t*, uint8_t* const*, const size_t*, int64_t*);
+static int64_t (*p_encode_pcm)(lhip_stream*, int, const void*, const void*, size_t, uint8_t*, size_t);
+static int (*p_encode_batch_pcm)(lhip_stream* const*, size_t, int, const void* const*, const void* const*, const size_t*, uint8_t* const*, const size_t*, int64_t*);
 static int (*p_flush_batch)(lhip_stream* const*, size_t, uint8_t* const*, const size_t*, int64_t*);
 static const char* (*p_last_error)(void);
 static int (*p_set_devices)(uint64_t);
@@ -62,7 +64,7 @@ static int load_lib(napi_env env) {
     SYM(p_encode_batch, "lhip_encode_batch") SYM(p_flush_batch, "lhip_flush_batch") SYM(p_set_devices, "lhip_set_devices")
     SYM(p_state_bytes, "lhip_state_bytes") SYM(p_state_get, "lhip_state_get") SYM(p_state_set, "lhip_state_set")
     SYM(p_seek_tail, "lhip_seek_tail_samples") SYM(p_seek, "lhip_seek") SYM(p_out_bytes, "lhip_encode_output_bytes")
-    SYM(p_call_limit, "lhip_frac_call_limit")
+    SYM(p_call_limit, "lhip_frac_call_limit") SYM(p_encode_pcm, "lhip_encode_pcm") SYM(p_encode_batch_pcm, "lhip_encode_batch_pcm")
 #undef SYM
     return 1;
 }
@@ -120,7 +122,16 @@ static napi_value make_i8(napi_env env, const uint8_t* src, size_t n) {
  * the library writes the frames straight into it: one allocation per call, no intermediate buffer, no copy -- and the caller still owns
  * a fresh array per call, which is the one semantic of the reference's `new Int8Array(mp3buf.subarray(0, _sz))` (index.js:129) to keep.
  * Only when the count is not known beforehand (bit-reservoir extension) or the call fails is the result copied into an exact array. */
-static napi_value encode_into_new_array(napi_env env, lhip_stream* s, const int16_t* dl, const int16_t* dr, size_t nl) {
+/* Sample formats (include/lamejs_hip.h, LHIP_PCM_*): an Int16Array goes the way it always went (lhip_encode), a Float32Array and interleaved
+ * input through lhip_encode_pcm.  A Float32 sample outside the contract (not finite, beyond +-131072) is refused before anything is consumed:
+ * that throws a RangeError with the library's text -- the one deviation from the reference on this path. */
+static int64_t encode_fmt(lhip_stream* s, int fmt, const void* dl, const void* dr, size_t nl, uint8_t* out, size_t cap) {
+    return fmt == LHIP_PCM_S16 ? p_encode(s, (const int16_t*)dl, (const int16_t*)dr, nl, out, cap) : p_encode_pcm(s, fmt, dl, dr, nl, out, cap);
+}
+/* -4 because a Float32 sample was refused (the library's text says so) -- every other -4 is swallowed into an empty array, as for Int16 input */
+static int refused_sample(int64_t rc, int fmt) { return rc == -4 && (fmt & LHIP_PCM_F32) && strstr(p_last_error(), "Float32 sample") != NULL; }
+static int pcm_type(napi_typedarray_type tt) { return tt == napi_int16_array ? LHIP_PCM_S16 : tt == napi_float32_array ? LHIP_PCM_F32 : -1; }
+static napi_value encode_into_new_array(napi_env env, lhip_stream* s, int fmt, const void* dl, const void* dr, size_t nl) {
     static uint8_t none[16];
     const int64_t want = p_out_bytes(s, nl);
     const size_t cap = want > 0 ? (size_t)want : 0;
@@ -132,33 +143,45 @@ static napi_value encode_into_new_array(napi_env env, lhip_stream* s, const int1
          * zero-filled ArrayBuffer of the bound per call would be allocated only to be thrown away */
         uint8_t* tmp = (uint8_t*)malloc(cap);
         if (!tmp) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-        const int64_t m = p_encode(s, dl, dr, nl, tmp, cap);
-        napi_value r = make_i8(env, tmp, m > 0 ? (size_t)m : 0);
+        const int64_t m = encode_fmt(s, fmt, dl, dr, nl, tmp, cap);
+        napi_value r = refused_sample(m, fmt) ? NULL : make_i8(env, tmp, m > 0 ? (size_t)m : 0);
         free(tmp);
+        if (!r) napi_throw_range_error(env, NULL, p_last_error());
         return r;
     }
     napi_value ab, ta; void* data = NULL;
     if (napi_create_arraybuffer(env, cap, &data, &ab) != napi_ok || (cap && !data)) { napi_throw_error(env, NULL, "could not allocate the output buffer"); return NULL; }
-    const int64_t n = p_encode(s, dl, dr, nl, cap ? (uint8_t*)data : none, cap);
+    const int64_t n = encode_fmt(s, fmt, dl, dr, nl, cap ? (uint8_t*)data : none, cap);
+    if (refused_sample(n, fmt)) { napi_throw_range_error(env, NULL, p_last_error()); return NULL; }
     /* the reference swallows negative codes and returns an empty array (index.js:128-129) */
     if (n != (int64_t)cap) return make_i8(env, (const uint8_t*)data, n > 0 ? (size_t)n : 0);
     if (napi_create_typedarray(env, napi_int8_array, cap, ab, 0, &ta) != napi_ok) { napi_throw_error(env, NULL, "could not create the output Int8Array"); return NULL; }
     return ta;
 }
 
+/* encode(handle, left, right|null[, interleavedChannels]): left / right Int16Array or Float32Array (both of one type); interleavedChannels > 0:
+ * left holds that many channels interleaved (L R L R ...), right is ignored */
 static napi_value js_encode(napi_env env, napi_callback_info info) {
-    size_t argc = 3; napi_value argv[3];
+    size_t argc = 4; napi_value argv[4];
     napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
     lhip_stream* s = NULL;
     if (argc < 2 || napi_get_value_external(env, argv[0], (void**)&s) != napi_ok || !s) { napi_throw_type_error(env, NULL, "first argument must be a stream handle"); return NULL; }
     napi_typedarray_type tt; size_t nl = 0, nr = 0; void *dl = NULL, *dr = NULL;
-    if (napi_get_typedarray_info(env, argv[1], &tt, &nl, &dl, NULL, NULL) != napi_ok || tt != napi_int16_array) { napi_throw_type_error(env, NULL, "left must be an Int16Array"); return NULL; }
+    if (napi_get_typedarray_info(env, argv[1], &tt, &nl, &dl, NULL, NULL) != napi_ok || pcm_type(tt) < 0) { napi_throw_type_error(env, NULL, "left must be an Int16Array or a Float32Array"); return NULL; }
+    int fmt = pcm_type(tt);
+    int32_t inter = 0;
+    if (argc > 3) { napi_valuetype v3; napi_typeof(env, argv[3], &v3); if (v3 == napi_number) napi_get_value_int32(env, argv[3], &inter); }
+    if (inter > 0) {
+        if (inter > 2 || nl % (size_t)inter) { napi_throw_type_error(env, NULL, "interleaved samples: the length must be a multiple of the channel count"); return NULL; }
+        return encode_into_new_array(env, s, fmt | LHIP_PCM_INTERLEAVED, dl, NULL, nl / (size_t)inter);
+    }
     napi_valuetype vt = napi_undefined;
     if (argc > 2) napi_typeof(env, argv[2], &vt);
     if (vt != napi_null && vt != napi_undefined) {
-        if (napi_get_typedarray_info(env, argv[2], &tt, &nr, &dr, NULL, NULL) != napi_ok || tt != napi_int16_array || nr != nl) { napi_throw_type_error(env, NULL, "right must be an Int16Array of the same length"); return NULL; }
+        const napi_typedarray_type tl = tt;
+        if (napi_get_typedarray_info(env, argv[2], &tt, &nr, &dr, NULL, NULL) != napi_ok || tt != tl || nr != nl) { napi_throw_type_error(env, NULL, tl == napi_int16_array ? "right must be an Int16Array of the same length" : "right must be a Float32Array of the same length"); return NULL; }
     }
-    return encode_into_new_array(env, s, (const int16_t*)dl, (const int16_t*)dr, nl);
+    return encode_into_new_array(env, s, fmt, dl, dr, nl);
 }
 
 static napi_value js_flush(napi_env env, napi_callback_info info) {
@@ -179,9 +202,11 @@ static napi_value js_flush(napi_env env, napi_callback_info info) {
  * call must share one configuration and device (the library checks); a failed call throws (there is no reference behaviour to
  * mirror for it), a stream without completed frames gets an empty array. */
 static napi_value batch_common(napi_env env, napi_callback_info info, int is_flush) {
-    size_t argc = 3; napi_value argv[3];
+    size_t argc = 4; napi_value argv[4];
     napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
     uint32_t n = 0;
+    int fmt = -1; int32_t inter = 0;         /* encodeBatch: the arrays' common type; 4th argument > 0: that many channels interleaved in lefts[i] */
+    if (!is_flush && argc > 3) { napi_valuetype v3; napi_typeof(env, argv[3], &v3); if (v3 == napi_number) napi_get_value_int32(env, argv[3], &inter); }
     if (argc < 1 || napi_get_array_length(env, argv[0], &n) != napi_ok) { napi_throw_type_error(env, NULL, "handles must be an array"); return NULL; }
     napi_value result; napi_create_array_with_length(env, n, &result);
     if (n == 0) return result;
@@ -192,7 +217,7 @@ static napi_value batch_common(napi_env env, napi_callback_info info, int is_flu
         if (argc > 2) { napi_valuetype vt; napi_typeof(env, argv[2], &vt); have_right = (vt != napi_null && vt != napi_undefined); }
     }
     lhip_stream** hs = (lhip_stream**)calloc(n, sizeof *hs);
-    const int16_t** L = (const int16_t**)calloc(n, sizeof *L); const int16_t** R = (const int16_t**)calloc(n, sizeof *R);
+    const void** L = (const void**)calloc(n, sizeof *L); const void** R = (const void**)calloc(n, sizeof *R);
     size_t* ns = (size_t*)calloc(n, sizeof *ns); size_t* caps = (size_t*)calloc(n, sizeof *caps);
     uint8_t** outs = (uint8_t**)calloc(n, sizeof *outs); int64_t* wr = (int64_t*)calloc(n, sizeof *wr);
     napi_value* abs_ = (napi_value*)calloc(n, sizeof *abs_);
@@ -204,14 +229,18 @@ static napi_value batch_common(napi_env env, napi_callback_info info, int is_flu
         if (!is_flush) {
             napi_value a; napi_typedarray_type tt; void* d = NULL;
             napi_get_element(env, argv[1], i, &a);
-            if (napi_get_typedarray_info(env, a, &tt, &ns[i], &d, NULL, NULL) != napi_ok || tt != napi_int16_array) { err = "lefts must hold Int16Arrays"; break; }
-            L[i] = (const int16_t*)d;
-            if (have_right) {
+            if (napi_get_typedarray_info(env, a, &tt, &ns[i], &d, NULL, NULL) != napi_ok || pcm_type(tt) < 0 || (fmt >= 0 && pcm_type(tt) != fmt)) { err = "lefts must hold Int16Arrays, or Float32Arrays throughout"; break; }
+            fmt = pcm_type(tt);
+            L[i] = d;
+            if (inter > 0) {
+                if (inter > 2 || ns[i] % (size_t)inter) { err = "interleaved samples: the length must be a multiple of the channel count"; break; }
+                ns[i] /= (size_t)inter;
+            } else if (have_right) {
                 size_t nr = 0; void* dr = NULL; napi_valuetype vt;
                 napi_get_element(env, argv[2], i, &a); napi_typeof(env, a, &vt);
                 if (vt != napi_null && vt != napi_undefined) {
-                    if (napi_get_typedarray_info(env, a, &tt, &nr, &dr, NULL, NULL) != napi_ok || tt != napi_int16_array || nr != ns[i]) { err = "rights must hold Int16Arrays as long as their lefts"; break; }
-                    R[i] = (const int16_t*)dr;
+                    if (napi_get_typedarray_info(env, a, &tt, &nr, &dr, NULL, NULL) != napi_ok || pcm_type(tt) != fmt || nr != ns[i]) { err = "rights must hold arrays of their lefts' type and length"; break; }
+                    R[i] = dr;
                 }
             }
         }
@@ -229,9 +258,13 @@ static napi_value batch_common(napi_env env, napi_callback_info info, int is_flu
             outs[i] = caps[i] ? (uint8_t*)data : none;
         }
     }
+    int range_err = 0;
     if (!err) {
-        const int rc = is_flush ? p_flush_batch(hs, n, outs, caps, wr) : p_encode_batch(hs, n, L, R, ns, outs, caps, wr);
-        if (rc != 0) err = p_last_error();
+        const int f = fmt | (inter > 0 ? LHIP_PCM_INTERLEAVED : 0);
+        const int rc = is_flush ? p_flush_batch(hs, n, outs, caps, wr)
+                     : f == LHIP_PCM_S16 ? p_encode_batch(hs, n, (const int16_t* const*)L, (const int16_t* const*)R, ns, outs, caps, wr)
+                                         : p_encode_batch_pcm(hs, n, f, L, R, ns, outs, caps, wr);
+        if (rc != 0) { err = p_last_error(); range_err = !is_flush && (f & LHIP_PCM_F32) && rc == -4 && strstr(err, "Float32 sample") != NULL; }
     }
     if (!err) for (uint32_t i = 0; i < n; i++) {
         napi_value ta;
@@ -240,7 +273,7 @@ static napi_value batch_common(napi_env env, napi_callback_info info, int is_flu
     }
     for (uint32_t i = 0; i < n; i++) if (outs[i] && outs[i] != none && (is_flush || !abs_[i])) free(outs[i]);      /* scratch buffers (flush; bit-reservoir streams) */
     free(hs); free(L); free(R); free(ns); free(caps); free(outs); free(wr); free(abs_);
-    if (err) { napi_throw_error(env, NULL, err); return NULL; }
+    if (err) { if (range_err) napi_throw_range_error(env, NULL, err); else napi_throw_error(env, NULL, err); return NULL; }
     return result;
 }
 /* Frame-range sharding of one stream (include/lamejs_hip.h: lhip_seek / lhip_state_get / lhip_state_set).  Unlike encode(), these

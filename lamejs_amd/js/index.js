@@ -27,6 +27,12 @@
  * throughput is in encodeBatch() over many such streams, of any mix of configurations; the flush frames the reference makes of its own NaN
  * samples are replaced by silent frames of equal length and header, and the stream ends with flush().  Not with { pendingFrames }
  * (re-chunking changes the bytes) or { reservoir }; no seek / getState / setState.  For every other triple the option changes nothing.
+ * Samples.  encodeBuffer() takes what the reference takes: its lame_encode_buffer stores whatever numbers it is given into a Float32Array
+ * (Lame.js:1506-1510) and encodes that.  An Int16Array goes to the GPU as it is; a Float32Array as it is (fractional parts and values beyond 16
+ * bits included: the reference's bytes for those values); anything else (Array, Float64Array, other typed arrays) through Float32Array.from,
+ * which is the reference's own store.  The one deviation: a sample that is not finite or lies beyond +-131072 throws a RangeError and
+ * consumes nothing (the reference encodes NaN into garbage).  Extension encodeInterleaved(samples): channels * n samples as they lie in a
+ * WAV file (L R L R ...), Int16Array or Float32Array, read in place by the kernels.
  */
 'use strict';
 const path = require('path');
@@ -48,6 +54,18 @@ function tablesBlob(channels, samplerate, kbps, opts) {
     let blob = blobCache.get(key);
     if (!blob) { blob = tables.buildBlob(channels, samplerate, kbps, opts).blob; blobCache.set(key, blob); }
     return blob;
+}
+
+/* one call's arrays in one sample type: Int16Array if all of them are, otherwise Float32Array (Int16 values are exact in Float32) */
+const isPcm = (a) => a instanceof Int16Array || a instanceof Float32Array;
+const toF32 = (a) => (a instanceof Float32Array ? a : Float32Array.from(a));
+function sameType(arrays) {
+    return arrays.every((a) => a instanceof Int16Array) ? arrays : arrays.map(toF32);
+}
+const PCM_LIMIT = 131072;
+function checkF32(a, what) {
+    for (let i = 0; i < a.length; i++)
+        if (!(Math.abs(a[i]) <= PCM_LIMIT)) throw new RangeError('lamejs_amd: Float32 sample outside the contract (finite, |x| <= 131072): ' + what + ' index ' + i + ', value ' + a[i] + '; nothing was consumed');
 }
 
 function Mp3Encoder(channels, samplerate, kbps, opts) {
@@ -80,12 +98,21 @@ function Mp3Encoder(channels, samplerate, kbps, opts) {
      * return its bytes in front of their own; getState / setState / seek refuse while input is pending: the state would not contain it) */
     if (pendMax) { hooks.drain = drain; hooks.pending = () => pendN; }
     const noPending = (what) => { if (pendN > 0) throw new Error(what + ': ' + pendN + ' samples are held back by { pendingFrames }; call flush() first'); };
+    /* { pendingFrames }: Int16 input is held back in Int16 buffers; at the first other input what is held back moves into Float32 buffers, which
+     * then serve for the rest of the stream (Int16 values are exact in Float32: the byte stream does not change) */
+    function pendToF32() {
+        const l = new Float32Array(pendL.length); l.set(pendL.subarray(0, pendN)); pendL = l;
+        if (pendR) { const r = new Float32Array(pendR.length); r.set(pendR.subarray(0, pendN)); pendR = r; }
+    }
     this.encodeBuffer = function (left, right) {
         if (channels == 1) right = null;
-        if (!(left instanceof Int16Array)) left = Int16Array.from(left);
-        if (right && !(right instanceof Int16Array)) right = Int16Array.from(right);
+        [left, right] = sameType(right ? [left, right] : [left]);
         if (!pendMax) return native.encode(handle, left, right || null);
         if (right && right.length != left.length) throw new TypeError('right must be an Int16Array of the same length');       /* (the native path's own check and message) */
+        if (left instanceof Float32Array) {                      /* checked before it is held back: a refused sample consumes nothing */
+            checkF32(left, 'left'); if (right) checkF32(right, 'right');
+            if (pendL instanceof Int16Array) pendToF32();
+        }
         if (left.length > pendL.length - pendN) {                /* does not fit beside what is pending: encode that first, then this */
             const a = drain(), b = left.length >= pendMax ? native.encode(handle, left, right || null) : null;
             if (b) { const r = new Int8Array(a.length + b.length); r.set(a, 0); r.set(b, a.length); return r; }
@@ -94,6 +121,16 @@ function Mp3Encoder(channels, samplerate, kbps, opts) {
         }
         pendL.set(left, pendN); if (pendR) pendR.set(right || left, pendN); pendN += left.length;
         return pendN >= pendMax ? drain() : EMPTY();
+    };
+    /* Extension: channels * n samples interleaved (L R L R ...), Int16Array or Float32Array (anything else through Float32Array.from) */
+    this.encodeInterleaved = function (samples) {
+        if (!isPcm(samples)) samples = Float32Array.from(samples);
+        if (samples.length % channels) throw new TypeError('interleaved samples: the length must be a multiple of the channel count');
+        if (!pendMax) return native.encode(handle, samples, null, channels);
+        if (channels == 1) return this.encodeBuffer(samples);
+        const n = samples.length / 2, l = new samples.constructor(n), r = new samples.constructor(n);      /* held back per channel, like everything { pendingFrames } holds back */
+        for (let i = 0; i < n; i++) { l[i] = samples[2 * i]; r[i] = samples[2 * i + 1]; }
+        return this.encodeBuffer(l, r);
     };
     this.flush = function () {
         if (!pendMax || pendN == 0) return native.flush(handle);
@@ -143,8 +180,11 @@ module.exports.deviceCount = function () { return loadAddon().deviceCount(); };
  * Extensions (not part of the reference API) for callers with many independent streams (BASELINE config 5):
  *   setDevice(d)                          encoders constructed afterwards live on HIP device d (deal streams round-robin
  *                                         over deviceCount() GPUs; streams never exchange data)
- *   encodeBatch(encoders, lefts[, rights]) one launch for all the encoders' new samples -> Int8Array per encoder, the same
- *                                         bytes each encoder's own encodeBuffer() would have returned
+ *   encodeBatch(encoders, lefts[, rights][, { interleaved: true }])
+ *                                         one launch for all the encoders' new samples -> Int8Array per encoder, the same
+ *                                         bytes each encoder's own encodeBuffer() would have returned.  Int16 if every array is an
+ *                                         Int16Array, otherwise the whole batch as Float32 (still one launch); interleaved: lefts[i]
+ *                                         holds channels * n samples (L R L R ...), rights is ignored
  *   flushBatch(encoders)                  likewise for flush()
  *   setDevices(mask)                      let the library deal new encoders round-robin over the GPUs named by the bit mask
  * The encoders of one call must share (channels, samplerate, kbps) and the device ({ fractionalResample } streams: the device only).
@@ -158,12 +198,17 @@ function drainPending(encoders) { return encoders.map((e) => (e._lhip.pending() 
 function prepend(heads, outs) {
     return outs.map((b, i) => { const a = heads[i]; if (!a || a.length == 0) return b; const r = new Int8Array(a.length + b.length); r.set(a, 0); r.set(b, a.length); return r; });
 }
-module.exports.encodeBatch = function (encoders, lefts, rights) {
+module.exports.encodeBatch = function (encoders, lefts, rights, opts) {
+    if (rights && !Array.isArray(rights) && typeof rights == 'object' && opts === undefined) { opts = rights; rights = null; }
     const hs = encoders.map((e) => e._lhip.handle);
-    const L = lefts.map((a) => (a instanceof Int16Array ? a : Int16Array.from(a)));
-    const stereo = encoders.length > 0 && encoders[0]._lhip.channels == 2;
-    const R = stereo && rights ? rights.map((a) => (a instanceof Int16Array ? a : Int16Array.from(a))) : null;
+    const channels = encoders.length > 0 ? encoders[0]._lhip.channels : 1;
+    const inter = !!(opts && opts.interleaved);
+    const nl = lefts.length;
+    const all = sameType(lefts.concat(channels == 2 && rights && !inter ? rights : []).map((a) => (isPcm(a) ? a : Float32Array.from(a))));
+    const L = all.slice(0, nl), R = all.length > nl ? all.slice(nl) : null;
+    /* checked BEFORE anything held back by { pendingFrames } is encoded: a refused sample consumes nothing, held-back input included */
+    if (L.length > 0 && L[0] instanceof Float32Array) { L.forEach((a, i) => checkF32(a, 'stream ' + i + ', left')); if (R) R.forEach((a, i) => checkF32(a, 'stream ' + i + ', right')); }
     const heads = drainPending(encoders);
-    return prepend(heads, loadAddon().encodeBatch(hs, L, R));
+    return prepend(heads, loadAddon().encodeBatch(hs, L, R, inter ? channels : 0));
 };
 module.exports.flushBatch = function (encoders) { const heads = drainPending(encoders); return prepend(heads, loadAddon().flushBatch(encoders.map((e) => e._lhip.handle))); };
