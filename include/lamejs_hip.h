@@ -39,6 +39,15 @@
  * Sample formats.  lhip_encode takes Int16 planes; lhip_encode_pcm and the *_pcm batch entries take Int16 or Float32, planar or interleaved
  * (see LHIP_PCM_* below): Float32 is what the reference itself encodes, so fractional samples and samples beyond 16 bits give its bytes.
  *
+ * Input gains and downmix (extension).  A blob built with { downmix, scale, scaleLeft, scaleRight } (tables.js) carries the reference's
+ * gfp.scale / scale_left / scale_right and, for a downmix, MPEGMode.MONO with two input channels (Lame.js:1551-1584).  lhip_config.channels
+ * counts INPUT channels: a downmix stream is created with channels = 2, takes two-channel calls through every entry below and is a
+ * one-channel stream behind the read sites (output sizes, state).  Per sample, in the reference's order, each product an f64 product stored to
+ * Float32:  a = l (* scale) (* scale_left);  b = r (* scale, only when two channels go out) (* scale_right);  downmix m = (float)(0.5 * (a + b)).
+ * lhip_create returns -3 with a message for a gain that is not finite, a negative scale, or a combined gain of a channel above 4 in
+ * magnitude; the Float32 sample limit of such a stream is 131072 / max(1, |gain left|, |gain right|).  lhip_seek applies the same arithmetic
+ * to its Int16 tails (a downmix stream needs both).
+ *
  * Semantics preserved: any chunking of the same sample stream yields the same bytes; a call
  * returns the bytes of all whole frames completed by that call (possibly 0); errors are negative
  * return codes mirroring the reference (-1 output buffer too small, -3 bad handle, -4 internal/device
@@ -60,7 +69,7 @@ extern "C" {
 typedef struct lhip_stream lhip_stream;
 
 typedef struct lhip_config {
-    int32_t channels;     /* 1 or 2 (as passed to Mp3Encoder) */
+    int32_t channels;     /* 1 or 2 (as passed to Mp3Encoder): INPUT channels -- 2 for a downmix blob */
     int32_t samplerate;   /* Hz */
     int32_t kbps;         /* CBR bitrate */
     int32_t device;       /* HIP device ordinal; -1 = current device */

@@ -116,7 +116,13 @@ def blob_is_current(blob: bytes) -> bool:
     return False
 
 
-def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, reservoir: bool = False, fractional_resample: bool = False) -> bytes:
+def _gain_text(g) -> str:
+    """A gain as tables.js reads it back exactly (``Number(repr)``); also the blob cache's file-name part."""
+    return repr(float(g))
+
+
+def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, reservoir: bool = False, fractional_resample: bool = False,
+                downmix: bool = False, scale=None, scale_left=None, scale_right=None) -> bytes:
     """The LHTB table blob for a configuration.
 
     Built by the host-side JavaScript ``lamejs_amd/js/tables.js`` (so every transcendental comes
@@ -126,14 +132,21 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     ``Mp3Encoder`` never selects it, index.js:105); only meaningful for two channels.
     ``fractional_resample``: accept the configurations that resample by a non-integer ratio (extension, call-sequence-exact:
     ``{ fractionalResample: true }`` of tables.js); for every other configuration the blob is the same with and without it.
+    ``downmix`` (two channels in, mono out), ``scale``, ``scale_left``, ``scale_right``: the reference's input gains and downmix
+    (``{ downmix, scale, scaleLeft, scaleRight }`` of tables.js); without them the blob is the bytes it always was.
     """
+    if downmix and channels != 2:
+        raise TypeError("downmix needs two input channels")
+    if downmix and joint:
+        raise TypeError("downmix and joint cannot be combined")
     joint = bool(joint) and channels == 2
     frac = bool(fractional_resample)
-    f = _TABLE_DIR / f"t_{channels}_{samplerate}_{kbps}{'_joint' if joint else ''}{'_resv' if reservoir else ''}{'_frac' if frac else ''}.bin"
+    mix = (["downmix"] if downmix else []) + [f"{k}={_gain_text(v)}" for k, v in (("scale", scale), ("scaleLeft", scale_left), ("scaleRight", scale_right)) if v is not None]
+    f = _TABLE_DIR / f"t_{channels}_{samplerate}_{kbps}{'_joint' if joint else ''}{'_resv' if reservoir else ''}{'_frac' if frac else ''}{''.join('_' + m.replace('=', '') for m in mix)}.bin"
     if not f.exists() or not blob_is_current(f.read_bytes()):      # a cached blob made by another version of its generator is stale
         _TABLE_DIR.mkdir(exist_ok=True)
         try:
-            subprocess.run(["node", str(_PKG / "js" / "tables.js"), str(channels), str(samplerate), str(kbps), str(f)] + (["joint"] if joint else []) + (["reservoir"] if reservoir else []) + (["fracresample"] if frac else []),
+            subprocess.run(["node", str(_PKG / "js" / "tables.js"), str(channels), str(samplerate), str(kbps), str(f)] + (["joint"] if joint else []) + (["reservoir"] if reservoir else []) + (["fracresample"] if frac else []) + mix,
                            check=True, capture_output=True, text=True)
         except (OSError, subprocess.CalledProcessError) as e:  # pragma: no cover
             msg = getattr(e, "stderr", "") or str(e)
@@ -174,7 +187,7 @@ class Mp3Encoder:
     """Mirror of the reference's ``Mp3Encoder`` (index.js:66-136)."""
 
     def __init__(self, channels: int = 1, samplerate: int = 44100, kbps: int = 128, device: int = -1, lib=None, joint: bool = False, reservoir: bool = False,
-                 fractional_resample: bool = False):
+                 fractional_resample: bool = False, downmix: bool = False, scale=None, scale_left=None, scale_right=None):
         """``joint`` (extension, not in the reference's wrapper): encode two channels in the reference's joint-stereo mode --
         per frame mid/side or left/right, as its encoder core decides when asked for MPEGMode.JOINT_STEREO.
         ``reservoir`` (extension): encode with the bit reservoir in use (the reference's wrapper disables it, index.js:108); the frames
@@ -182,11 +195,15 @@ class Mp3Encoder:
         ``fractional_resample`` (extension): accept the configurations the reference resamples by a non-integer ratio, as call-sequence
         streams -- each ``encodeBuffer`` gives the reference's bytes for the same sequence of call lengths, a call longer than the
         reference consumes whole raises (``call_limit()`` samples are always accepted), each call completes at most one frame, and the
-        stream ends with ``flush()`` (include/lamejs_hip.h)."""
+        stream ends with ``flush()`` (include/lamejs_hip.h).
+        ``downmix`` (extension, two channels): the reference's MPEGMode.MONO for two input channels -- ``encodeBuffer(l, r)`` and
+        ``encode_interleaved`` take both channels, the stream is a mono stream of ``0.5 * (l + r)`` mixed where the samples are read.
+        ``scale``, ``scale_left``, ``scale_right`` (extension): the reference's ``gfp.scale`` (replaces the preset's) and per-channel
+        gains, applied in its order and with its roundings (include/lamejs_hip.h, "Input gains and downmix")."""
         self._lib = lib or load_library()
         self.channels, self.samplerate, self.kbps = int(channels), int(samplerate), int(kbps)
         self._resv = bool(reservoir)
-        blob = tables_blob(self.channels, self.samplerate, self.kbps, joint, reservoir, fractional_resample)
+        blob = tables_blob(self.channels, self.samplerate, self.kbps, joint, reservoir, fractional_resample, downmix, scale, scale_left, scale_right)
         cfg = _Config(self.channels, self.samplerate, self.kbps, device)
         h = ctypes.c_void_p()
         buf = ctypes.create_string_buffer(blob, len(blob))

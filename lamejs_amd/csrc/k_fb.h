@@ -166,28 +166,32 @@ template <int ROW> LHIP_DEV void poly_slot(const Tables& T, const float* xt, flo
     for (int i = 0; i < 32; i++) out[i] = a[i];
 }
 // kb_poly_run's staging where everything staged is new input, per sample format (F32: Float32 / Int16; UNIT: stride 1 known at compile time --
-// <0, 1> is the Int16 planar loop as it always was).  Eight loads in flight per lane: with one load per trip (the trip count is not a
-// compile-time constant) the wave waited out a full memory latency 36 times, which was most of this kernel's time
-template <int F32, int UNIT>
+// <0, 1, 0> is the Int16 planar loop as it always was) and per input treatment (MIX: PcmSrc::mix -- 0 `scale` at most, 1 the channel's own gain
+// follows, 2 downmix: a second source, eight more loads in flight).  Eight loads in flight per lane and source: with one load per trip (the
+// trip count is not a compile-time constant) the wave waited out a full memory latency 36 times, which was most of this kernel's time
+template <int F32, int UNIT, int MIX>
 LHIP_DEV void poly_stage_new(const PcmSrc& P, int first, int lo, int n_need, int lane, float* xs) {
     typedef typename std::conditional<F32 != 0, float, int16_t>::type elem_t;
     const int str = UNIT ? 1 : P.stride;
     const elem_t* src = (const elem_t*)P.src + (int64_t)first * str;
+    const elem_t* src2 = (const elem_t*)(MIX == 2 ? P.src2 : P.src) + (int64_t)first * str;
     enum { STG = 8 };
     for (int n0 = 0; n0 < n_need; n0 += LHIP_NL * STG) {
-        typename std::conditional<F32 != 0, float, int>::type raw[STG];
+        typename std::conditional<F32 != 0, float, int>::type raw[STG], rawb[STG];        // (rawb: downmix only; never loaded otherwise)
 #pragma unroll
         for (int k = 0; k < STG; k++) {                  // unconditional loads from a clamped index: a predicated load is waited for inside its branch
             const int n = n0 + lane + LHIP_NL * k;
             raw[k] = src[(n < lo ? lo : (n < n_need ? n : n_need - 1)) * str];
+            if (MIX == 2) rawb[k] = src2[(n < lo ? lo : (n < n_need ? n : n_need - 1)) * str];
         }
 #pragma unroll
-        for (int k = 0; k < STG; k++) LHIP_PIN_LOADED(raw[k]);
+        for (int k = 0; k < STG; k++) { LHIP_PIN_LOADED(raw[k]); if (MIX == 2) LHIP_PIN_LOADED(rawb[k]); }
 #pragma unroll
         for (int k = 0; k < STG; k++) {
             const int n = n0 + lane + LHIP_NL * k;
-            float v = F32 ? pcm_f32_clean((float)raw[k]) : (float)raw[k];
+            float v = F32 ? pcm_f32_clean((float)raw[k], P.limit) : (float)raw[k];
             if (P.do_scale) v = (float)((double)v * P.scale);
+            if (MIX) v = pcm_mix(P, v, MIX == 2 ? (F32 ? pcm_f32_clean((float)rawb[k], P.limit) : (float)rawb[k]) : 0.f);
             if (n < lo) v = 0.f;                            // (0 * scale could be -0 or NaN for an odd scale; the slot is defined as +0)
             if (n < n_need) xs[(n & 31) * POLY_ROW + (n >> 5)] = v;
         }
@@ -206,9 +210,17 @@ LHIP_DEV void kb_poly_run(const Tables& T, const Workspace& W, const StreamDesc*
     const int n_need = POLY_N1 + 576 * (cnt - 1);
     wave_sync();
     if (!P.plane && s0 + lo >= P.mf) {                        // wave-uniform usual case: everything staged is new input
-        if (!P.f32 && P.stride == 1) poly_stage_new<0, 1>(P, s0 - P.mf, lo, n_need, lane, L.xs);
-        else if (!P.f32) poly_stage_new<0, 0>(P, s0 - P.mf, lo, n_need, lane, L.xs);
-        else poly_stage_new<1, 0>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+        if (!P.mix) {
+            if (!P.f32 && P.stride == 1) poly_stage_new<0, 1, 0>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+            else if (!P.f32) poly_stage_new<0, 0, 0>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+            else poly_stage_new<1, 0, 0>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+        } else if (P.mix == 1) {                                // gains / downmix: the stride stays a run-time value (two instances each, not three)
+            if (!P.f32) poly_stage_new<0, 0, 1>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+            else poly_stage_new<1, 0, 1>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+        } else {
+            if (!P.f32) poly_stage_new<0, 0, 2>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+            else poly_stage_new<1, 0, 2>(P, s0 - P.mf, lo, n_need, lane, L.xs);
+        }
     } else {
         for (int n = lane; n < n_need; n += LHIP_NL) L.xs[(n & 31) * POLY_ROW + (n >> 5)] = (n >= lo) ? pcm_at(P, s0 + n) : 0.f;
     }

@@ -164,15 +164,42 @@ template <int K> LHIP_DEV int guarded_f32_of_sum(const double (&p)[K], double sc
 }
 
 // kb_psyA's staging of a window that lies wholly in the call's new samples, per sample format (F32: Float32 / Int16; UNIT: stride 1 known
-// at compile time -- <0, 1> is the Int16 planar loop as it always was)
-template <int F32, int UNIT>
+// at compile time -- <0, 1, 0> is the Int16 planar loop as it always was) and per input treatment (MIX: PcmSrc::mix -- 1 the channel's own gain
+// follows `scale`, 2 downmix).  The downmix instance is unrolled by hand: the trip count (16) is known, and left as one load per source and
+// trip each trip would wait out two memory latencies -- eight loads in flight per source instead
+template <int F32, int UNIT, int MIX>
 LHIP_DEV void psya_stage_new(const PcmSrc& P, int first, int lane, float* fz) {
     typedef typename std::conditional<F32 != 0, float, int16_t>::type elem_t;
     const int str = UNIT ? 1 : P.stride;
     const elem_t* src = (const elem_t*)P.src + (int64_t)first * str;
+    if (MIX == 2) {
+        const elem_t* src2 = (const elem_t*)P.src2 + (int64_t)first * str;
+        enum { STG = 8 };
+        for (int i0 = lane; i0 < BLKSIZE; i0 += LHIP_NL * STG) {
+            typename std::conditional<F32 != 0, float, int>::type ra[STG], rb[STG];
+#pragma unroll
+            for (int k = 0; k < STG; k++) {
+                int i = i0 + LHIP_NL * k;
+                if (i >= BLKSIZE) i = BLKSIZE - 1;                // (one lane: the last trips of the scalar build; never on a 64-lane wave)
+                ra[k] = src[i * str]; rb[k] = src2[i * str];
+            }
+#pragma unroll
+            for (int k = 0; k < STG; k++) { LHIP_PIN_LOADED(ra[k]); LHIP_PIN_LOADED(rb[k]); }
+#pragma unroll
+            for (int k = 0; k < STG; k++) {
+                const int i = i0 + LHIP_NL * k;
+                float v = F32 ? pcm_f32_clean((float)ra[k], P.limit) : (float)ra[k];
+                if (P.do_scale) v = (float)((double)v * P.scale);
+                v = pcm_mix(P, v, F32 ? pcm_f32_clean((float)rb[k], P.limit) : (float)rb[k]);
+                if (i < BLKSIZE) fz[i] = v;
+            }
+        }
+        return;
+    }
     for (int i = lane; i < BLKSIZE; i += LHIP_NL) {
-        float v = F32 ? pcm_f32_clean((float)src[i * str]) : (float)src[i * str];
+        float v = F32 ? pcm_f32_clean((float)src[i * str], P.limit) : (float)src[i * str];
         if (P.do_scale) v = (float)((double)v * P.scale);
+        if (MIX) v = pcm_mix(P, v, 0.f);
         fz[i] = v;
     }
 }
@@ -199,9 +226,17 @@ LHIP_DEV void kb_psyA(const Tables& T, const Workspace& W, const StreamDesc* SD,
         const int b0 = 576 * q + 304;
         if (!P.plane && b0 >= P.mf) {
             // the usual case, wave-uniform: the whole window lies in this call's new samples -- no per-sample decisions
-            if (!P.f32 && P.stride == 1) psya_stage_new<0, 1>(P, b0 - P.mf, lane, L.fz);
-            else if (!P.f32) psya_stage_new<0, 0>(P, b0 - P.mf, lane, L.fz);
-            else psya_stage_new<1, 0>(P, b0 - P.mf, lane, L.fz);
+            if (!P.mix) {
+                if (!P.f32 && P.stride == 1) psya_stage_new<0, 1, 0>(P, b0 - P.mf, lane, L.fz);
+                else if (!P.f32) psya_stage_new<0, 0, 0>(P, b0 - P.mf, lane, L.fz);
+                else psya_stage_new<1, 0, 0>(P, b0 - P.mf, lane, L.fz);
+            } else if (P.mix == 1) {
+                if (!P.f32) psya_stage_new<0, 0, 1>(P, b0 - P.mf, lane, L.fz);
+                else psya_stage_new<1, 0, 1>(P, b0 - P.mf, lane, L.fz);
+            } else {
+                if (!P.f32) psya_stage_new<0, 0, 2>(P, b0 - P.mf, lane, L.fz);
+                else psya_stage_new<1, 0, 2>(P, b0 - P.mf, lane, L.fz);
+            }
         } else {
             for (int i = lane; i < BLKSIZE; i += LHIP_NL) L.fz[i] = pcm_at(P, b0 + i);
         }

@@ -29,6 +29,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <chrono>
+#include <cmath>
 
 using namespace lhip;
 
@@ -148,17 +149,17 @@ LHIP_DEV void kb_load(const Tables& T, const Workspace& W, const StreamDesc* SD,
 //     out[m] = sum_{i=0..32} x[m*r + i - 16] * blackfilt[1][i]        (x[<0] = 0; f64 accumulation in tap order)
 // and emits out[m] as soon as m*r + 16 < (samples received so far).  `p0` is the position of tap 0 of this call's
 // first output relative to this call's first input sample; positions < 0 are the carried tail of earlier calls.
+// (gains and downmix happen in front of fill_buffer, Lame.js:1551-1584: the filter reads mixed samples -- pcm_new_at -- and `old` holds mixed samples)
 template <int F32>
-LHIP_DEV void kb_resample_elem(const Tables& T, float* dst, const void* src, int stride, const float* old, int p0, int64_t t) {
+LHIP_DEV void kb_resample_elem(const Tables& T, float* dst, const PcmSrc& P, const float* old, int p0, int64_t t) {
     const float* coef = T.rs_blackfilt + T.rs_bpc * RS_TAPS;
     const int64_t p = (int64_t)p0 + t * T.rs_ratio;
-    const bool do_scale = !(T.scale == 0.0) && !(T.scale == 1.0);
     double xvalue = 0.0;
     for (int i = 0; i < RS_TAPS; i++) {
         const int64_t q = p + i;
         float y;
         if (q < 0) y = old[(RS_TAPS - 1) + q];
-        else { y = pcm_new(src, F32, stride, q); if (do_scale) y = (float)((double)y * T.scale); }
+        else y = pcm_new_at<F32>(P, q);
         xvalue += (double)y * (double)coef[i];
     }
     dst[t] = (float)xvalue;
@@ -171,7 +172,7 @@ LHIP_DEV void kb_resample_elem(const Tables& T, float* dst, const void* src, int
 // -0.5 and +0.5.  That is why call boundaries show in the bytes and such a stream is a call-sequence stream.  The host only asks for outputs
 // whose taps lie inside the call (j + 15.5 < n_in, at most 31 samples back into the carried tail); the clamps keep a wrong record in bounds.
 template <int F32>
-LHIP_DEV void kb_resample_frac_elem(const Tables& T, float* dst, const void* src, int stride, const float* old, double itime, int n_in, int64_t k) {
+LHIP_DEV void kb_resample_frac_elem(const Tables& T, float* dst, const PcmSrc& P, const float* old, double itime, int n_in, int64_t k) {
     enum { BLACKSIZE = RS_TAPS - 1 };
     const int bpc = T.rs_bpc;
     const double time0 = (double)k * T.resample_ratio;
@@ -180,13 +181,12 @@ LHIP_DEV void kb_resample_frac_elem(const Tables& T, float* dst, const void* src
     int joff = (int)floor((offset * 2 * bpc) + bpc + .5);
     joff = joff < 0 ? 0 : (joff > 2 * bpc ? 2 * bpc : joff);
     const float* coef = T.rs_blackfilt + (int64_t)joff * BLACKSIZE;
-    const bool do_scale = !(T.scale == 0.0) && !(T.scale == 1.0);
     double xvalue = 0.0;
     for (int i = 0; i < BLACKSIZE; i++) {
         const int j2 = (int)(i + j - 15.5);
         float y = 0.f;
         if (j2 < 0) { if (j2 >= -BLACKSIZE) y = old[BLACKSIZE + j2]; }
-        else if (j2 < n_in) { y = pcm_new(src, F32, stride, j2); if (do_scale) y = (float)((double)y * T.scale); }
+        else if (j2 < n_in) y = pcm_new_at<F32>(P, j2);
         xvalue += (double)y * (double)coef[i];
     }
     dst[k] = (float)xvalue;
@@ -200,14 +200,14 @@ LHIP_DEV void kb_prep_stream(const Tables& T, const Workspace& W, const StreamDe
     const int64_t off = SD[st].pcm_off + io.mf_size;
     for (int ch = 0; ch < C; ch++) {
         float* dst = W.pcm + (int64_t)ch * W.pcm_plane + off;
-        const void* src = ch ? io.src[1] : io.src[0];
+        const PcmSrc P = pcm_source_new(T, io, ch);
         const float* old = io.state->rs_old[ch];
         if (io.f32) {                                            // the sample type is decided outside the tap loops
-            if (T.rs_frac) for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_frac_elem<1>(T, dst, src, io.stride, old, io.rs_itime, io.n_in, i);
-            else for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_elem<1>(T, dst, src, io.stride, old, io.rs_p0, i);
+            if (T.rs_frac) for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_frac_elem<1>(T, dst, P, old, io.rs_itime, io.n_in, i);
+            else for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_elem<1>(T, dst, P, old, io.rs_p0, i);
         } else {
-            if (T.rs_frac) for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_frac_elem<0>(T, dst, src, io.stride, old, io.rs_itime, io.n_in, i);
-            else for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_elem<0>(T, dst, src, io.stride, old, io.rs_p0, i);
+            if (T.rs_frac) for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_frac_elem<0>(T, dst, P, old, io.rs_itime, io.n_in, i);
+            else for (int64_t i = tid; i < io.n_new; i += nthreads) kb_resample_elem<0>(T, dst, P, old, io.rs_p0, i);
         }
     }
 }
@@ -218,8 +218,8 @@ LHIP_DEV void kb_prep(const Tables& T, const Workspace& W, const StreamDesc* SD,
 // Float32 input by device pointer (lhip_encode_batch_device_pcm): the host cannot see the values, the read sites read a sample outside the
 // contract as +0 (pcm_f32_clean) -- this counts them, once per (stream, channel, sample) the caller handed over, for lhip_last_batch_rejected_samples.  A pass of its own
 // over the call's input (4.6 KB per two-channel frame), launched for such calls only: the read sites stay free of atomics, and several of them
-// read a sample more than once.
-LHIP_DEV unsigned long long kb_count_rejected(const StreamIO* IO, int nstreams, int C, int64_t tid, int64_t nthreads) {
+// read a sample more than once.  C: INPUT channels -- source positions are counted, both source channels of a downmix; limit: Tables::pcm_limit.
+LHIP_DEV unsigned long long kb_count_rejected(const StreamIO* IO, int nstreams, int C, float limit, int64_t tid, int64_t nthreads) {
     unsigned long long bad = 0;
     for (int st = 0; st < nstreams; st++) {
         const StreamIO io = IO[st];
@@ -227,7 +227,7 @@ LHIP_DEV unsigned long long kb_count_rejected(const StreamIO* IO, int nstreams, 
         for (int ch = 0; ch < C; ch++) {
             if (ch && io.src[1] == io.src[0]) continue;          // right == left (or no right plane): the samples exist once, as for the host entries' scan
             const float* src = (const float*)(ch ? io.src[1] : io.src[0]);
-            for (int64_t i = tid; i < io.n_in; i += nthreads) { const float v = src[i * io.stride]; bad += !((v < 0 ? -v : v) <= PCM_F32_LIMIT); }
+            for (int64_t i = tid; i < io.n_in; i += nthreads) { const float v = src[i * io.stride]; bad += !((v < 0 ? -v : v) <= limit); }
         }
     }
     return bad;
@@ -289,20 +289,21 @@ LHIP_DEV void kb_save(const Tables& T, const Workspace& W, const StreamDesc* SD,
     }
     if (T.rs_ratio != 1 && SAVE_JOB()) {
         // the last 32 input samples seen so far (carried tail ++ this call's input), as the scaled floats the filter reads
-        const bool do_scale = !(T.scale == 0.0) && !(T.scale == 1.0);
-        for (int ch = 0; ch < C; ch++)
+        for (int ch = 0; ch < C; ch++) {
+            const PcmSrc P = pcm_source_new(T, io, ch);
             for (int base = 0; base < RS_TAPS - 1; base += LHIP_NL) {
                 const int i = base + lane;
                 float v = 0.f;
                 if (i < RS_TAPS - 1) {
                     const int64_t q = (int64_t)io.n_in - (RS_TAPS - 1) + i;
                     if (q < 0) v = S->rs_old[ch][(RS_TAPS - 1) + q];
-                    else { v = pcm_new(ch ? io.src[1] : io.src[0], io.f32, io.stride, q); if (do_scale) v = (float)((double)v * T.scale); }
+                    else v = io.f32 ? pcm_new_at<1>(P, q) : pcm_new_at<0>(P, q);
                 }
                 wave_sync();
                 if (i < RS_TAPS - 1) S->rs_old[ch][i] = v;
                 wave_sync();
             }
+        }
     }
 #undef SAVE_JOB
 }
@@ -610,8 +611,8 @@ __global__ __launch_bounds__(64 * WPB) void g_psyA(Tables T, Workspace W, const 
 __global__ __launch_bounds__(256) void g_prep(Tables T, Workspace W, const StreamDesc* SD, const StreamIO* IO, int nstreams) {
     kb_prep(T, W, SD, IO, nstreams, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
-__global__ __launch_bounds__(256) void g_count_rejected(const StreamIO* IO, int nstreams, int C, unsigned long long* ctr) {
-    const unsigned long long bad = kb_count_rejected(IO, nstreams, C, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+__global__ __launch_bounds__(256) void g_count_rejected(const StreamIO* IO, int nstreams, int C, float limit, unsigned long long* ctr) {
+    const unsigned long long bad = kb_count_rejected(IO, nstreams, C, limit, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
     if (bad) atomicAdd(ctr, bad);
 }
 __global__ __launch_bounds__(64) void g_scan_raw(Tables T, Workspace W, const StreamDesc* SD, int ngs) { const int g = blockIdx.x * 64 + threadIdx.x; if (g < ngs) kb_scan_raw(T, W, SD, g); }
@@ -991,6 +992,7 @@ struct TableSet {
     void* d_qtabs = nullptr;
     int device = 0;
     int base_frame_bytes = 0;
+    bool bad_gain = false;  // build_tables refused the blob's input gains (lhip_create: -3)
     ~TableSet() { rt::dfree(d_blob); rt::dfree(d_extra); rt::dfree(d_qtabs); }
 };
 
@@ -1021,6 +1023,7 @@ static bool build_tables(TableSet& ts, const void* blob, size_t nbytes, const lh
         return (const uint8_t*)ts.d_blob + e->offset;
     };
     auto host_arr = [&](const char* name) -> const void* { const lhtb_entry* e = find_entry(b, name); return e ? b + e->offset : nullptr; };
+    bool optional = false;               // an entry that only blobs built with the option have: missing is -1, not an error
     auto named = [&](const char* names_key, const char* key) -> int {
         const lhtb_entry* e = find_entry(b, names_key);
         if (!e) { ok = false; return 0; }
@@ -1034,6 +1037,7 @@ static bool build_tables(TableSet& ts, const void* blob, size_t nbytes, const lh
             if (all.compare(pos, c - pos, key) == 0) return idx;
             idx++; pos = c + 1;
         }
+        if (optional) return -1;
         set_err(std::string("tables blob: config key missing: ") + key); ok = false; return 0;
     };
     const int32_t* ci = (const int32_t*)host_arr("cfg_i");
@@ -1052,6 +1056,17 @@ static bool build_tables(TableSet& ts, const void* blob, size_t nbytes, const lh
     CD(scale); CD(attackthre); CD(attackthre_s); CD(interChRatio); CD(masking_lower_long); CD(masking_lower_short);
     CD(ATH_aaSensitivityP); CD(ATH_floor); CD(decay); CD(ma_max_i1); CD(ma_max_i2); CD(ma_max_m); CD(VO_SCALE);
     CD(msfix); CD(ATHlower);
+    // input gains and downmix (extension): entries that exist only in blobs built with { downmix, scale, scaleLeft, scaleRight }.  Without them:
+    // as many channels come in as go out, the preset's scale is in force by the plain comparison (which agrees with the reference's NEQ for
+    // every preset value), no per-channel gain.
+    optional = true;
+#define CIO(f, dflt) { const int k_ = named("cfg_i_names", #f); T.f = k_ >= 0 ? ci[k_] : (dflt); }
+#define CDO(f, dflt) { const int k_ = named("cfg_d_names", #f); T.f = k_ >= 0 ? cd[k_] : (dflt); }
+    CIO(channels_in, T.channels_out); CIO(do_scale, (!(T.scale == 0.0) && !(T.scale == 1.0)) ? 1 : 0); CIO(do_scale_left, 0); CIO(do_scale_right, 0);
+    CDO(scale_left, 0.0); CDO(scale_right, 0.0);
+#undef CIO
+#undef CDO
+    optional = false;
 #undef CI
 #undef CD
 #define AF(f) T.f = (const float*)arr(#f, 2, nullptr)
@@ -1077,7 +1092,23 @@ static bool build_tables(TableSet& ts, const void* blob, size_t nbytes, const lh
     if (!((T.mode == 0 && T.channels_out == 2) || (T.mode == 1 && T.channels_out == 2) || (T.mode == 3 && T.channels_out == 1))) { set_err("configuration outside the supported envelope (channel mode)"); return false; }
     T.psy_channels = (T.mode == 1) ? 4 : T.channels_out;
     // ---- envelope checks: fail loudly rather than produce different bytes than the reference ----
-    if (T.channels_out != (cfg.channels == 1 ? 1 : 2) || T.in_samplerate != cfg.samplerate || T.brate <= 0) { set_err("tables blob does not match the requested configuration"); return false; }
+    // (cfg.channels counts INPUT channels: a downmix blob has channels_in = 2, channels_out = 1)
+    if (!(T.channels_in == T.channels_out || (T.channels_in == 2 && T.channels_out == 1))) { set_err("tables blob: channels_in does not fit channels_out"); return false; }
+    if (T.channels_in != (cfg.channels == 1 ? 1 : 2) || T.in_samplerate != cfg.samplerate || T.brate <= 0) { set_err("tables blob does not match the requested configuration"); return false; }
+    // input gains: samples behind the gains must stay inside the range every kernel was proven for, |x| <= PCM_F32_LIMIT
+    {
+        T.do_scale = T.do_scale != 0; T.do_scale_left = T.do_scale_left != 0; T.do_scale_right = T.do_scale_right != 0;
+        if (T.channels_in == 1) T.do_scale_right = 0;                       // one input channel: scale_right is dead
+        const bool down = T.channels_in == 2 && T.channels_out == 1;
+        if (!std::isfinite(T.scale) || !std::isfinite(T.scale_left) || !std::isfinite(T.scale_right)) { set_err("input gains: scale, scale_left and scale_right must be finite"); ts.bad_gain = true; return false; }
+        if (T.scale < 0) { set_err("input gains: scale must not be negative (the reference asserts scale >= 0)"); ts.bad_gain = true; return false; }
+        const double gl = (T.do_scale ? T.scale : 1.0) * (T.do_scale_left ? T.scale_left : 1.0);
+        const double gr = ((T.do_scale && !down) ? T.scale : 1.0) * (T.do_scale_right ? T.scale_right : 1.0);     // the reference's downmix exception: `scale` never reaches the right samples
+        const double g = fmax(1.0, fmax(fabs(gl), fabs(gr)));
+        if (g > 4.0) { set_err("input gains: the combined gain of a channel must not exceed 4 in magnitude (Int16 full scale then ends exactly at the sample limit, 131072)"); ts.bad_gain = true; return false; }
+        T.pcm_limit = (float)((double)PCM_F32_LIMIT / g);
+        T.in_mix = down ? 2 : ((T.do_scale_left || T.do_scale_right) ? 1 : 0);
+    }
     // resampling (Lame.js:1849): only integer decimation ratios, where the reference's filter is a fixed 33-tap FIR
     // (extension: a blob built with { fractionalResample } carries the reference's set-up for a non-integer ratio -- filter_l = 31 and all
     //  2 * bpc + 1 windows; such a stream is a call-sequence stream, see frac_pass)
@@ -1441,6 +1472,7 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     TableSet& ts = *jobs[0].s->ts;
     const Tables& T = ts.T;
     const int C = T.channels_out;
+    const int Cin = T.channels_in;                 // channels the caller hands over (2 with C == 1: downmix); everything that sizes or copies INPUT goes by it
     const int GR = T.mode_gr, frame = 576 * GR, mf_needed = 1024 + frame - 272;   // calcNeeded (Lame.js:1517-1530)
     const int S = (int)jobs.size();
     const bool resv = !T.disable_reservoir;       // bit reservoir (extension): the frames of a stream are a serial chain (g_resv_stream), output sizes known to the device only
@@ -1479,7 +1511,7 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
         if (j.F > maxF) maxF = j.F;
         pcm_plane += (total + 63) & ~(int64_t)63;
         in_total += (int64_t)j.n; out_total += (j.bytes + 15) & ~(int64_t)15;
-        in_bytes += (j.n * (size_t)C * fmt_bps(j.f32) + 3) & ~(size_t)3;
+        in_bytes += (j.n * (size_t)Cin * fmt_bps(j.f32) + 3) & ~(size_t)3;
         count_rej |= j.count_rejected && j.f32 && j.n > 0;
     }
     // ---- workspace ----
@@ -1553,10 +1585,10 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
         o.rs_itime = j.s->rs_itime;
         out_rel[i] = sd[i].out_off;
         const size_t bps = fmt_bps(j.f32);
-        const bool il = j.inter && C == 2;            // (one channel: interleaved is planar)
+        const bool il = j.inter && Cin == 2;          // (one channel: interleaved is planar)
         o.f32 = j.f32 ? 1 : 0; o.stride = il ? 2 : 1;
         if (dev_io) {
-            o.src[0] = j.l; o.src[1] = il ? (const void*)((const uint8_t*)j.l + bps) : ((C == 2 && j.r) ? j.r : j.l); o.out = j.out;
+            o.src[0] = j.l; o.src[1] = il ? (const void*)((const uint8_t*)j.l + bps) : ((Cin == 2 && j.r) ? j.r : j.l); o.out = j.out;
         } else {
             uint8_t* base = small ? smb + sm_in : (uint8_t*)ws.in16.p;
             uint8_t* hbase = small ? pin + (sm_in - sm_nfl) : nullptr;
@@ -1566,7 +1598,7 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
             else if (!rt::h2d((void*)o.src[0], j.l, plane, st)) return false;
             if (il) o.src[1] = base + in_off + bps;
             in_off += plane;
-            if (C == 2 && !il) {
+            if (Cin == 2 && !il) {
                 o.src[1] = base + in_off;
                 if (small) memcpy(hbase + in_off, j.r ? j.r : j.l, plane);
                 else if (!rt::h2d((void*)o.src[1], j.r ? j.r : j.l, plane, st)) return false;
@@ -1614,13 +1646,13 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     g_rejected = 0; g_rej_pending = nullptr;
     if (count_rej) {
 #ifdef LHIP_HOSTSIM
-        g_rejected = (int64_t)kb_count_rejected(dIO, S, C, 0, 1);
+        g_rejected = (int64_t)kb_count_rejected(dIO, S, Cin, T.pcm_limit, 0, 1);
 #else
         if (!ws.rejected.ensure(64) || !rt::dzero(ws.rejected.p, 8, st)) return false;
         int64_t nb = (in_total + 255) / 256;
         if (nb > 2048) nb = 2048;
         if (nb < 1) nb = 1;
-        LAUNCHB(KT_COUNT, g_count_rejected, (int)nb, 256, st, dIO, S, C, (unsigned long long*)ws.rejected.p);
+        LAUNCHB(KT_COUNT, g_count_rejected, (int)nb, 256, st, dIO, S, Cin, T.pcm_limit, (unsigned long long*)ws.rejected.p);
         g_rej_pending = ctx;
 #endif
     }
@@ -2028,11 +2060,11 @@ int lhip_create(const lhip_config* cfg, const void* tables, size_t tables_bytes,
     if (it != ctx->tables.end()) {
         ts = it->second;
         // the same checks build_tables makes of the blob against the requested configuration
-        if (ts->T.channels_out != (cfg->channels == 1 ? 1 : 2) || ts->T.in_samplerate != cfg->samplerate) { set_err("tables blob does not match the requested configuration"); return LHIP_ERR_INTERNAL; }
+        if (ts->T.channels_in != (cfg->channels == 1 ? 1 : 2) || ts->T.in_samplerate != cfg->samplerate) { set_err("tables blob does not match the requested configuration"); return LHIP_ERR_INTERNAL; }
     } else {
         ts = std::make_shared<TableSet>();
         ts->device = dev;
-        if (!build_tables(*ts, tables, tables_bytes, *cfg, ctx->stream)) return LHIP_ERR_INTERNAL;
+        if (!build_tables(*ts, tables, tables_bytes, *cfg, ctx->stream)) return ts->bad_gain ? -3 : LHIP_ERR_INTERNAL;      // (-3: a gain outside the contract, with a message)
         ctx->tables[key] = ts;
     }
     std::unique_ptr<lhip_stream> s(new lhip_stream());
@@ -2201,7 +2233,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
     std::lock_guard<std::mutex> chunk_lk(ctx->chunk_mu);
     const size_t NS = strs.size();
     const Tables& T = strs[0]->ts->T;
-    const int C = T.channels_out;
+    const int C = T.channels_in;                   // this function only moves INPUT: a downmix stream hands over two channels
     const size_t obytes = (size_t)(strs[0]->ts->base_frame_bytes + 1);
     const size_t spf = (size_t)576 * T.mode_gr * T.rs_ratio;             // input samples per frame
     // staging halves sized for the largest unit of THIS call: samples per channel (pieces back to back, each rounded up to 64) and output bytes
@@ -2333,12 +2365,12 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
 static int64_t encode_host_chunked(lhip_stream* s, int format, const void* left, const void* right, size_t nsamples, uint8_t* out, size_t out_cap) {
     const Tables& T = s->ts->T;
     const ChunkSchedule& cfg = host_chunk_schedule();
-    const size_t mul = (!cfg.fixed && T.channels_out == 2) ? 2 : 1;
+    const size_t mul = (!cfg.fixed && T.channels_out == 2) ? 2 : 1;      // (the schedule follows the encode's cost: output channels)
     const size_t spf = (size_t)576 * T.mode_gr * T.rs_ratio;
     // the whole call must fit the caller's buffer BEFORE anything is consumed (a failed call consumes nothing)
     if ((size_t)batch_bytes(*s->ts, s->slot_lag, call_frames(s, nsamples)) > out_cap) { set_err("output buffer too small"); return LHIP_ERR_BUFFER_TOO_SMALL; }
     std::vector<std::vector<HostPiece>> units;
-    const bool il = (format & LHIP_PCM_INTERLEAVED) && T.channels_out == 2;
+    const bool il = (format & LHIP_PCM_INTERLEAVED) && T.channels_in == 2;
     const size_t step = fmt_bps(format & LHIP_PCM_F32) * (il ? 2 : 1);       // bytes from one sample position of the call to the next
     {
         const size_t cap = cfg.cap * mul * spf;
@@ -2386,24 +2418,25 @@ static int encode_host_groups(lhip_stream* const* streams, size_t n, int format,
 
 // Float32 input through a host pointer: the whole call is looked at before anything is consumed.  A sample that is not finite or lies beyond
 // +-131072 refuses the call (the reference encodes NaN and infinities into garbage; here they never reach a kernel).  `count` elements.
-static bool scan_f32(const void* p, size_t count, size_t* where) {
+static bool scan_f32(const void* p, size_t count, float limit, size_t* where) {
     const float* f = (const float*)p;
-    for (size_t i = 0; i < count; i++) if (!((f[i] < 0 ? -f[i] : f[i]) <= PCM_F32_LIMIT)) { *where = i; return false; }
+    for (size_t i = 0; i < count; i++) if (!((f[i] < 0 ? -f[i] : f[i]) <= limit)) { *where = i; return false; }
     return true;
 }
 // the host-pointer entries' check of one stream's input; on refusal lhip_last_error() names stream, channel, index and value
-static bool host_samples_ok(size_t stream_idx, int channels, int format, const void* left, const void* right, size_t n) {
+// (channels: INPUT channels; limit: the stream's Tables::pcm_limit -- 131072, or less where its gains exceed 1)
+static bool host_samples_ok(size_t stream_idx, int channels, float limit, int format, const void* left, const void* right, size_t n) {
     if (!(format & LHIP_PCM_F32) || n == 0 || !left) return true;
     const bool il = (format & LHIP_PCM_INTERLEAVED) && channels == 2;
     size_t w = 0;
     int ch = 0;
     const void* bad = nullptr;
-    if (!scan_f32(left, il ? 2 * n : n, &w)) { bad = left; if (il) { ch = (int)(w & 1); } }
-    else if (!il && channels == 2 && right && right != left && !scan_f32(right, n, &w)) { bad = right; ch = 1; }
+    if (!scan_f32(left, il ? 2 * n : n, limit, &w)) { bad = left; if (il) { ch = (int)(w & 1); } }
+    else if (!il && channels == 2 && right && right != left && !scan_f32(right, n, limit, &w)) { bad = right; ch = 1; }
     if (!bad) return true;
     char txt[256];
-    snprintf(txt, sizeof txt, "Float32 sample outside the contract (finite, |x| <= 131072): stream %zu, channel %d, index %zu, value %g; nothing was consumed",
-             stream_idx, ch, il ? w / 2 : w, (double)((const float*)bad)[w]);
+    snprintf(txt, sizeof txt, "Float32 sample outside the contract (finite, |x| <= %g): stream %zu, channel %d, index %zu, value %g; nothing was consumed",
+             (double)limit, stream_idx, ch, il ? w / 2 : w, (double)((const float*)bad)[w]);
     set_err(txt);
     return false;
 }
@@ -2413,7 +2446,7 @@ int64_t lhip_encode_pcm(lhip_stream* s, int format, const void* left, const void
     if (!fmt_ok(format)) { set_err("unknown sample format"); return LHIP_ERR_INTERNAL; }
     if (nsamples == 0) return 0;
     if (!left) { set_err("null input"); return LHIP_ERR_INTERNAL; }
-    if (!host_samples_ok(0, s->ts->T.channels_out, format, left, right, nsamples)) return LHIP_ERR_INTERNAL;
+    if (!host_samples_ok(0, s->ts->T.channels_in, s->ts->T.pcm_limit, format, left, right, nsamples)) return LHIP_ERR_INTERNAL;
     {
         static const bool no_chunk = []() { const char* e = getenv("LAMEJS_HIP_NO_HOST_CHUNKS"); return e && e[0] == '1'; }();
         const Tables& T = s->ts->T;
@@ -2606,7 +2639,7 @@ int lhip_encode_batch_pcm(lhip_stream* const* streams, size_t nstreams, int form
     if (!fmt_ok(format)) { set_err("unknown sample format"); return LHIP_ERR_INTERNAL; }
     if ((format & LHIP_PCM_F32) && streams && left && nsamples)       // every stream's samples are looked at before any stream consumes anything
         for (size_t i = 0; i < nstreams; i++)
-            if (streams[i] && streams[i]->magic == 0x4c484950 && !host_samples_ok(i, streams[i]->ts->T.channels_out, format, left[i], right ? right[i] : nullptr, nsamples[i])) {
+            if (streams[i] && streams[i]->magic == 0x4c484950 && !host_samples_ok(i, streams[i]->ts->T.channels_in, streams[i]->ts->T.pcm_limit, format, left[i], right ? right[i] : nullptr, nsamples[i])) {
                 for (size_t k = 0; k < nstreams; k++) if (written) written[k] = LHIP_ERR_INTERNAL;
                 return LHIP_ERR_INTERNAL;
             }
@@ -2754,12 +2787,25 @@ int lhip_seek(lhip_stream* s, int64_t sample_pos, const int16_t* tail_left, cons
     if (T.rs_ratio != 1 || !T.disable_reservoir) { set_err("lhip_seek: not for resampling or bit-reservoir streams"); return LHIP_ERR_INTERNAL; }
     if (s->frame_num != 0 || s->mf_size != MF_INIT) { set_err("lhip_seek: the stream has been used"); return LHIP_ERR_INTERNAL; }
     if (sample_pos < 2 * frame || sample_pos % frame != 0 || !tail_left) { set_err("lhip_seek: position must be a whole number (>= 2) of frames"); return LHIP_ERR_INTERNAL; }
-    if (T.channels_out == 2 && !tail_right) { set_err("lhip_seek: a two-channel stream needs both tails"); return LHIP_ERR_INTERNAL; }
-    const bool do_scale = !(T.scale == 0.0) && !(T.scale == 1.0);
+    if (T.channels_in == 2 && !tail_right) { set_err("lhip_seek: a two-channel stream needs both tails"); return LHIP_ERR_INTERNAL; }
+    // the tails as the kernels would have left them: behind gains and mix (the host's copy of pcm_new_at / pcm_mix, lhip_layout.h)
+    const bool down = T.in_mix == 2;
     std::vector<float> t((size_t)2 * MF_NEEDED, 0.f);
     for (int ch = 0; ch < T.channels_out; ch++) {
         const int16_t* src = (ch == 1 && tail_right) ? tail_right : tail_left;
-        for (int i = 0; i < ntail; i++) { float v = (float)src[i]; if (do_scale) v = (float)((double)v * T.scale); t[(size_t)ch * MF_NEEDED + i] = v; }
+        const bool do_g2 = ch ? T.do_scale_right : T.do_scale_left;
+        const double g2 = ch ? T.scale_right : T.scale_left;
+        for (int i = 0; i < ntail; i++) {
+            float v = (float)src[i];
+            if (T.do_scale) v = (float)((double)v * T.scale);
+            if (do_g2) v = (float)((double)v * g2);
+            if (down) {
+                float b = (float)tail_right[i];
+                if (T.do_scale_right) b = (float)((double)b * T.scale_right);
+                v = (float)(0.5 * ((double)v + (double)b));
+            }
+            t[(size_t)ch * MF_NEEDED + i] = v;
+        }
     }
     if (!rt::set_device(ctx->device) || !rt::h2d((uint8_t*)s->d_state + offsetof(StreamState, pcm_tail), t.data(), sizeof(float) * 2 * MF_NEEDED, ctx->stream) || !rt::sync(ctx->stream)) return LHIP_ERR_INTERNAL;
     const int64_t k = sample_pos / frame;                     // the stream has emitted k - 1 frames

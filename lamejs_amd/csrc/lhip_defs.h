@@ -114,6 +114,13 @@ struct Tables {
     const int32_t *bvtab;                   // count_bits: [289] by big_values / 2: a1 | a2 << 10 | region0_count << 20 | region1_count << 24 | sfb_count1 << 27
     const void *qtabs_img;                  // the quantization kernels' LDS tables (QuantTabs, k_quant.h) as one prebuilt image: a workgroup copies it flat instead of gathering it from the source tables
     const int32_t *fold_marks, *wpre;       // calc_noise's fold: band-start / band-end marks per lane [2][64]; widest band among bands 0 .. b [24 long | 40 short]
+    // input gains and downmix (extension; Lame.js:1551-1584; lhip_layout.h PcmSrc).  From the blob where it has the entries, defaults otherwise;
+    // at the end of the record so that nothing in front of them moves
+    double scale_left, scale_right;
+    int channels_in,                        // channels the caller hands over: channels_out, or 2 with channels_out == 1 (downmix)
+        do_scale, do_scale_left, do_scale_right,   // the gain is in force (the reference's NEQ(g, 0) && NEQ(g, 1), resolved by tables.js)
+        in_mix;                             // 0: `scale` at most / 1: per-channel gains / 2: downmix (PcmSrc::mix)
+    float pcm_limit;                        // Float32 input: |x| above this is outside the contract: PCM_F32_LIMIT / max(1, |gain left|, |gain right|)
 };
 
 // Per-granule-channel side information produced by the quantization kernel and consumed by the

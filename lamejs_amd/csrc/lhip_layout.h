@@ -77,7 +77,7 @@ struct StreamState {                // psy arrays hold 4 channels: L, R and -- j
 
 struct StreamIO {          // per stream, per launch (device array parallel to StreamDesc)
     StreamState* state;
-    const void* src[2];    // new samples (device addresses): first sample of channel 0 / 1 in the call's sample format
+    const void* src[2];    // new samples (device addresses): first sample of INPUT channel 0 / 1 in the call's sample format (a downmix stream has two sources and one channel)
     uint8_t* out;          // where this stream's frames go (device address)
     int32_t n_new, mf_size;    // samples appended to the encoder's buffer by this call / already buffered
     int32_t f32, stride;       // sample format of this call: 0 Int16 / 1 Float32; elements from one sample of a channel to the next (1 planar, 2 interleaved stereo)
@@ -95,26 +95,52 @@ struct StreamIO {          // per stream, per launch (device array parallel to S
 // 2, channel 1 starting one element after channel 0).  A Float32 sample outside the contract -- not finite, or |x| > PCM_F32_LIMIT --
 // is read as +0 at EVERY read site (pcm_f32_clean: one compare, false for NaN): nothing non-finite reaches a kernel's arithmetic.
 #define PCM_F32_LIMIT 131072.0f
-LHIP_DEV float pcm_f32_clean(float v) { return (v < 0 ? -v : v) <= PCM_F32_LIMIT ? v : 0.f; }
+// (`limit`: Tables::pcm_limit -- PCM_F32_LIMIT, or less on a stream whose gains exceed 1, so that samples BEHIND the gains stay within PCM_F32_LIMIT)
+LHIP_DEV float pcm_f32_clean(float v, float limit) { return (v < 0 ? -v : v) <= limit ? v : 0.f; }
 // new sample i of a channel, unscaled (F32 / stride: wave-uniform)
-LHIP_DEV float pcm_new(const void* src, int f32, int stride, int64_t i) {
-    if (f32) return pcm_f32_clean(((const float*)src)[i * stride]);
+LHIP_DEV float pcm_new(const void* src, int f32, int stride, int64_t i, float limit) {
+    if (f32) return pcm_f32_clean(((const float*)src)[i * stride], limit);
     return (float)((const int16_t*)src)[i * stride];
 }
+// Input gains and downmix (extension; Lame.js:1551-1584, in the reference's order and with its roundings -- every `*=` on its Float32Array is an
+// f64 product stored to Float32):   a = l;  a *= scale;  a *= scale_left;      b = r;  b *= scale (ONLY when two channels go out);  b *= scale_right;
+// downmix (two channels in, one out):  m = (float)(0.5 * ((double)a + (double)b)).  In a downmix the right samples therefore never see `scale`
+// (the preset's 0.95 at and below 128 kbps included): the reference's quirk, reproduced.  Which gains are in force is resolved on the host with the
+// reference's tolerant NEQ (tables.js); a rejected Float32 sample is zero BEFORE gain and mix.
 struct PcmSrc {
     const float* plane;      // != nullptr: materialised segment (resampling configurations)
-    const float* tail;       // carried samples [0, mf)
+    const float* tail;       // carried samples [0, mf): behind gains and mix already
     const void* src;         // new samples [mf, ...)
     int mf, do_scale;
     int f32, stride;         // StreamIO::f32, StreamIO::stride
     double scale;
+    int mix;                 // 0: `scale` at most (every stream built without the options) / 1: this channel's own gain may follow / 2: downmix
+    int do_g2, do_gb;        // this channel's gain (scale_left / scale_right) in force; downmix: scale_right in force on the other source
+    const void* src2;        // downmix: the right channel's new samples (same format and stride)
+    double g2, gb;
+    float limit;             // Tables::pcm_limit
 };
+// what follows `scale` on a stream with gains or downmix (P.mix != 0); `b`: the other source's sample, unscaled (downmix only)
+LHIP_DEV float pcm_mix(const PcmSrc& P, float a, float b) {
+    if (P.do_g2) a = (float)((double)a * P.g2);
+    if (P.mix == 2) {
+        if (P.do_gb) b = (float)((double)b * P.gb);
+        a = (float)(0.5 * ((double)a + (double)b));          // one rounding
+    }
+    return a;
+}
+// new sample i (>= 0) of the stream's channel as the encoder sees it: behind gains and mix
+template <int F32>
+LHIP_DEV float pcm_new_at(const PcmSrc& P, int64_t i) {
+    float v = pcm_new(P.src, F32, P.stride, i, P.limit);
+    if (P.do_scale) v = (float)((double)v * P.scale);
+    if (P.mix) v = pcm_mix(P, v, P.mix == 2 ? pcm_new(P.src2, F32, P.stride, i, P.limit) : 0.f);
+    return v;
+}
 LHIP_DEV float pcm_at(const PcmSrc& P, int s) {
     if (P.plane) return P.plane[s];
     if (s < P.mf) return P.tail[s];
-    float v = pcm_new(P.src, P.f32, P.stride, s - P.mf);
-    if (P.do_scale) v = (float)((double)v * P.scale);
-    return v;
+    return P.f32 ? pcm_new_at<1>(P, s - P.mf) : pcm_new_at<0>(P, s - P.mf);
 }
 
 // All slot arrays of a launch (device pointers).  C = channels_out.
@@ -188,11 +214,21 @@ LHIP_DEV int vd_gain(uint32_t h) { return (int)(h & 255u); }
 LHIP_DEV int vd_start(uint32_t h) { return (int)((h >> 8) & 255u); }
 LHIP_DEV int vd_step(uint32_t h) { return (int)((h >> 16) & 255u); }
 
-LHIP_DEV PcmSrc pcm_source(const Tables& T, const Workspace& W, const StreamDesc& sd, const StreamIO& io, int ch) {
+// the new samples of output channel ch of a stream (no plane, no tail: the resamplers and the state save read these directly)
+LHIP_DEV PcmSrc pcm_source_new(const Tables& T, const StreamIO& io, int ch) {
     PcmSrc P;
+    P.plane = nullptr; P.tail = nullptr;
+    P.src = ch ? io.src[1] : io.src[0]; P.mf = io.mf_size; P.f32 = io.f32; P.stride = io.stride;       // (not io.src[ch]: a dynamic index into a by-value copy of the record makes the copy a private array)
+    P.do_scale = T.do_scale; P.scale = T.scale;
+    P.mix = T.in_mix; P.src2 = io.src[1]; P.limit = T.pcm_limit;
+    P.do_g2 = ch ? T.do_scale_right : T.do_scale_left; P.g2 = ch ? T.scale_right : T.scale_left;
+    P.do_gb = T.do_scale_right; P.gb = T.scale_right;
+    return P;
+}
+LHIP_DEV PcmSrc pcm_source(const Tables& T, const Workspace& W, const StreamDesc& sd, const StreamIO& io, int ch) {
+    PcmSrc P = pcm_source_new(T, io, ch);
     P.plane = T.rs_ratio != 1 ? W.pcm + (int64_t)ch * W.pcm_plane + sd.pcm_off : nullptr;
-    P.tail = io.state->pcm_tail[ch]; P.src = ch ? io.src[1] : io.src[0]; P.mf = io.mf_size; P.f32 = io.f32; P.stride = io.stride;       // (not io.src[ch]: a dynamic index into a by-value copy of the record makes the copy a private array)
-    P.do_scale = !(T.scale == 0.0) && !(T.scale == 1.0); P.scale = T.scale;
+    P.tail = io.state->pcm_tail[ch];
     return P;
 }
 

@@ -20,6 +20,12 @@
  * sixty-four together take hardly longer.  The BYTE STREAM is the reference's (any chunking of the samples gives the same bytes); only
  * WHICH call returns which bytes changes: calls return empty arrays until N frames are pending, then all their frames at once, and
  * flush() returns the rest.  Off by default: without it every call returns exactly the bytes the reference's call returns.
+ * Extension { downmix, scale, scaleLeft, scaleRight }: the reference core's input gains and stereo-to-mono downmix (Lame.js:1551-1584), which
+ * its wrapper does not offer -- new Mp3Encoder(2, 44100, 64, { downmix: true, scale: 0.8, scaleLeft: 1, scaleRight: 0.5 }) takes two channels
+ * (encodeBuffer(l, r), encodeInterleaved, encodeBatch, { pendingFrames } holding source samples of both) and writes a mono stream, mixed where
+ * the samples are read on the device; byte for byte what the reference's core gives for MPEGMode.MONO with those gains.  `scale` replaces the
+ * preset's (0.95 at and below 128 kbps).  { downmix } with one channel or with { jointStereo } is a TypeError; a gain beyond 4 in magnitude,
+ * a negative scale or a gain that is not finite is refused at construction.
  * Extension { fractionalResample: true }: the 49 (channels, sample rate, kbps) triples the reference resamples by a non-integer ratio -- refused
  * by default, because the reference feeds itself NaN samples there once a call is long enough -- are accepted as call-sequence streams: every
  * encodeBuffer() gives the reference's bytes for the same sequence of call lengths; a call longer than the reference consumes whole throws
@@ -50,7 +56,8 @@ function loadAddon() {
  * between streams with identical blobs as well).  Configurations outside the envelope throw in buildBlob and are not cached. */
 const blobCache = new Map();
 function tablesBlob(channels, samplerate, kbps, opts) {
-    const key = [channels, samplerate, kbps, opts && opts.jointStereo ? 1 : 0, opts && opts.reservoir ? 1 : 0, opts && opts.fractionalResample ? 1 : 0].join('|');     /* (pendingFrames is host-side only) */
+    const key = [channels, samplerate, kbps, opts && opts.jointStereo ? 1 : 0, opts && opts.reservoir ? 1 : 0, opts && opts.fractionalResample ? 1 : 0,
+        opts && opts.downmix ? 1 : 0, opts ? String(opts.scale) : '', opts ? String(opts.scaleLeft) : '', opts ? String(opts.scaleRight) : ''].join('|');     /* (pendingFrames is host-side only) */
     let blob = blobCache.get(key);
     if (!blob) { blob = tables.buildBlob(channels, samplerate, kbps, opts).blob; blobCache.set(key, blob); }
     return blob;

@@ -78,6 +78,13 @@ function resolveParams(channels, samplerate, kbps, opts) {
     if (opts && opts.jointStereo && channels == 2) p.mode = MODE_JOINT_STEREO;
     /* extension (SURVEY.md 8f #4): the bit reservoir, which index.js:108 switches off */
     p.disable_reservoir = (opts && opts.reservoir) ? 0 : 1;
+    /* extension { downmix }: two channels in, MPEGMode.MONO out -- everything below resolves as the reference does for that mode
+     * (channels_out = 1, mono side info, presets and lowpass); the mix itself is Lame.js:1579-1584 */
+    if (opts && opts.downmix) {
+        if (channels != 2) throw new TypeError('lamejs_amd: { downmix } needs two input channels');
+        if (opts.jointStereo) throw new TypeError('lamejs_amd: { downmix } and { jointStereo } cannot be combined');
+        p.mode = MODE_MONO;
+    }
     p.channels_out = (p.mode == MODE_MONO) ? 1 : 2;
     p.in_samplerate = samplerate;
     let brate = kbps;
@@ -222,6 +229,20 @@ function resolveParams(channels, samplerate, kbps, opts) {
     p.attackthre = row[5];
     p.attackthre_s = row[6];
     p.scale = row[8];
+    /* extension { scale, scaleLeft, scaleRight }: gfp.scale / scale_left / scale_right (Lame.js:1551-1576).  The user's scale replaces the
+     * preset's, which is written only while gfp.scale is still -1 (Presets.js:313-316); a gain is in force when the reference's tolerant
+     * NEQ says so (BitStream.js:22-30), not `!=` */
+    {
+        const given = (k) => !!opts && opts[k] !== undefined && opts[k] !== null;
+        const num = (k) => { const v = opts[k]; if (typeof v != 'number') throw new TypeError('lamejs_amd: { ' + k + ' } must be a number'); return v; };
+        p.input_options = given('downmix') && opts.downmix || given('scale') || given('scaleLeft') || given('scaleRight') ? 1 : 0;
+        if (given('scale')) p.scale = num('scale');
+        p.scale_left = given('scaleLeft') ? num('scaleLeft') : 0.;          /* LameGlobalFlags.js:34, 38 */
+        p.scale_right = given('scaleRight') ? num('scaleRight') : 0.;
+        const EQ = (a, b) => (Math.abs(a) > Math.abs(b)) ? (Math.abs(a - b) <= Math.abs(a) * 1e-6) : (Math.abs(a - b) <= Math.abs(b) * 1e-6);
+        const inForce = (g) => (!EQ(g, 0) && !EQ(g, 1.0)) ? 1 : 0;
+        p.do_scale = inForce(p.scale); p.do_scale_left = inForce(p.scale_left); p.do_scale_right = inForce(p.scale_right);
+    }
     const maskingadjust = row[9];
     const maskingadjust_short = (row[9] > 0) ? row[9] * .9 : row[9] * 1.1;
     p.ATHlower = -row[10] / 10.;
@@ -625,6 +646,12 @@ function buildBlob(channels, samplerate, kbps, opts) {
         ma_max_m: T.ma_max_m, VO_SCALE: T.VO_SCALE, resample_ratio: p.resample_ratio,
         msfix: p.msfix, ATHlower: p.ATHlower
     };
+    /* input gains / downmix: named entries that exist only when an option asks for them (a blob without is the bytes it always was;
+     * the library defaults them) */
+    if (p.input_options) {
+        Object.assign(cfg_i, { channels_in: p.channels_in, do_scale: p.do_scale, do_scale_left: p.do_scale_left, do_scale_right: p.do_scale_right });
+        Object.assign(cfg_d, { scale_left: p.scale_left, scale_right: p.scale_right });
+    }
     const entries = [];
     entries.push(['cfg_i_names', Int32Array.from(Buffer.from(Object.keys(cfg_i).join(',') + '\0', 'ascii'))]);
     entries.push(['cfg_i', I(Object.values(cfg_i))]);
@@ -683,9 +710,12 @@ function fractionalCallLimit(p) {
 module.exports = { buildBlob, resolveParams, buildTables, packBlob, sourceHash, fractionalCallLimit };
 
 if (require.main === module) {
-    /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] [fracresample] */
+    /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] [fracresample] [downmix] [scale=G] [scaleLeft=G] [scaleRight=G] */
     const [ch, sr, kb, out] = process.argv.slice(2), flags = process.argv.slice(6);
-    const r = buildBlob(+ch, +sr, +kb, { jointStereo: flags.includes('joint'), reservoir: flags.includes('reservoir'), fractionalResample: flags.includes('fracresample') });
+    const opts = { jointStereo: flags.includes('joint'), reservoir: flags.includes('reservoir'), fractionalResample: flags.includes('fracresample') };
+    if (flags.includes('downmix')) opts.downmix = true;
+    for (const f of flags) { const m = /^(scale|scaleLeft|scaleRight)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
+    const r = buildBlob(+ch, +sr, +kb, opts);
     require('fs').writeFileSync(out, r.blob);
     console.log('wrote', out, r.blob.length, 'bytes');
 }

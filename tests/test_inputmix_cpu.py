@@ -1,0 +1,214 @@
+"""Input gains (scale, scale_left, scale_right) and the stereo-to-mono downmix (extension; Lame.js:1551-1584).  CPU tier: the blob, the
+reference goldens and a random family against the unchanged oracle on the kernel logic (host simulation, one lane; wave simulation, 64
+lanes), refusals, lhip_seek and the state record."""
+import ctypes
+import json
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import inputmix_cases as mc
+from conftest import ROOT
+from pcmformats_cases import F32, INTER, S16, encode_fmt
+
+NODE = shutil.which("node")
+RATES = [8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000]
+KBPS = [8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160, 192, 224, 256, 320]
+
+
+def _sim(name):
+    import lamejs_amd
+    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
+    lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / name)
+    assert b"HOST SIMULATION" in lib.lhip_version()
+    return lib
+
+
+@pytest.fixture(scope="module")
+def sim():
+    return _sim("liblamejs_hostsim.so")
+
+
+@pytest.fixture(scope="module")
+def wavesim():
+    return _sim("liblamejs_wavesim.so")
+
+
+@pytest.fixture(scope="module")
+def G():
+    return mc.goldens()
+
+
+def test_golden_set_is_the_one_asked_for(G):
+    names = {c["name"] for c in G}
+    assert {"downmix_44100_128_quirk", "downmix_44100_320", "downmix_48000_64", "downmix_44100_96", "downmix_16000_32_lsf", "downmix_8000_8", "gains_lr_128",
+            "gains_lr_320", "downmix_flip_left_double_right", "downmix_f32", "gains_f32", "downmix_44100_32_resample_int", "downmix_44100_48_resample_frac"} <= names
+    for sc in ("0.5", "1", "0", "1.0000005", "4"):
+        assert {f"scale_{sc}_mono", f"scale_{sc}_stereo"} <= names
+    by = {c["name"]: c for c in G}
+    assert by["downmix_44100_128_quirk"]["ref_scale"] == 0.95 and by["downmix_44100_128_quirk"]["ref_channels_out"] == 1
+    # the reference treats 1.0000005 and 0 as "no scaling": the bytes of scale 1
+    for ch in ("mono", "stereo"):
+        assert by[f"scale_1.0000005_{ch}"]["enc_md5"] == by[f"scale_1_{ch}"]["enc_md5"] == by[f"scale_0_{ch}"]["enc_md5"] != by[f"scale_0.5_{ch}"]["enc_md5"]
+    assert by["downmix_44100_32_resample_int"]["out_samplerate"] == 22050 and by["downmix_44100_48_resample_frac"]["out_samplerate"] == 32000
+    for c in G:
+        assert c["flush_len"] > 0 and (len(c["call_lens"]) == 23 if c["name"].endswith("_frac") else c["call_lens"] == [1152] * 8 + [3 * 1152 + 391])
+
+
+@pytest.mark.skipif(NODE is None, reason="node not available")
+def test_blob_without_the_options_is_unchanged_and_entries_appear_on_request():
+    """All 324 triples: a blob built without the new options has none of the new named entries and is the same bytes whether the options are
+    absent, undefined or `downmix: false`; with an option the six entries appear and nothing else changes size."""
+    js = ("const t = require(process.argv[1]); const out = [];"
+          "const names = (b, key) => { const n = b.readUInt32LE(8); for (let i = 0; i < n; i++) { const e = 16 + 48 * i; const nm = b.toString('ascii', e, e + 32).replace(/\\0.*$/, '');"
+          " if (nm == key) { const cnt = b.readUInt32LE(e + 36), off = b.readUInt32LE(e + 40); let s = ''; for (let k = 0; k < cnt; k++) { const c = b.readInt32LE(off + 4 * k); if (!c) break; s += String.fromCharCode(c); } return s; } } return null; };"
+          "for (const ch of [1, 2]) for (const sr of %s) for (const kb of %s) {"
+          " const a = t.buildBlob(ch, sr, kb, { fractionalResample: true }).blob, b = t.buildBlob(ch, sr, kb, { fractionalResample: true, downmix: false, scale: undefined, scaleLeft: undefined, scaleRight: null }).blob;"
+          " const c = t.buildBlob(ch, sr, kb, { fractionalResample: true, scaleLeft: 1 }).blob;"
+          " out.push([Buffer.compare(a, b) == 0 ? 1 : 0, /channels_in|do_scale|scale_left|scale_right/.test(names(a, 'cfg_i_names') + names(a, 'cfg_d_names')) ? 1 : 0,"
+          "  names(c, 'cfg_i_names').endsWith('disable_reservoir,channels_in,do_scale,do_scale_left,do_scale_right') ? 1 : 0, names(c, 'cfg_d_names').endsWith('ATHlower,scale_left,scale_right') ? 1 : 0]); }"
+          "console.log(JSON.stringify(out));" % (json.dumps(RATES), json.dumps(KBPS)))
+    r = subprocess.run([NODE, "-e", js, str(ROOT / "lamejs_amd" / "js" / "tables.js")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = json.loads(r.stdout)
+    assert len(rows) == 324 and all(x == [1, 0, 1, 1] for x in rows)
+
+
+@pytest.mark.skipif(NODE is None, reason="node not available")
+def test_tables_resolve_a_downmix_as_the_reference_resolves_mono():
+    """{ downmix } resolves everything as a one-channel configuration does (mode, side info, presets, lowpass, sample rate); the flags follow the
+    reference's tolerant NEQ; the user's scale replaces the preset's."""
+    js = ("const t = require(process.argv[1]); const pick = (p) => [p.mode, p.channels_out, p.channels_in, p.sideinfo_len, p.out_samplerate, p.lowpassfreq, p.scale, p.do_scale, p.do_scale_left, p.do_scale_right];"
+          "console.log(JSON.stringify([pick(t.resolveParams(2, 44100, 32, { downmix: true })), pick(t.resolveParams(1, 44100, 32, {})),"
+          " pick(t.resolveParams(2, 44100, 128, { scale: 1.0000005, scaleLeft: 0.9999995, scaleRight: 1e-9 })), pick(t.resolveParams(2, 44100, 128, { scale: 0 }))]));")
+    r = subprocess.run([NODE, "-e", js, str(ROOT / "lamejs_amd" / "js" / "tables.js")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    down, mono, tol, zero = json.loads(r.stdout)
+    assert down[:2] == mono[:2] == [3, 1] and down[2] == 2 and mono[2] == 1 and down[3:] == mono[3:] and down[7] == 1
+    assert tol[6:] == [1.0000005, 0, 0, 1] and zero[6:8] == [0, 0]
+
+
+def test_oracle_with_premix_reproduces_the_goldens(G):
+    """What makes the family's reference a reference: the unchanged oracle on a blob built with scale: 1, fed the numpy premix, gives the
+    golden bytes -- on every golden whose premix is whole Int16 numbers (the oracle takes nothing else)."""
+    ran = [c["name"] for c in G if mc.golden_premix_check(c)]
+    assert {"whole_downmix_quirk", "whole_gains_lr", "whole_downmix_flip", "whole_downmix_resample_int", "scale_1_mono", "scale_0_stereo", "scale_1.0000005_mono"} <= set(ran), ran
+
+
+def test_hostsim_every_golden(sim, G):
+    for i, c in enumerate(G):
+        mc.run_golden_case(sim, c, fmt_of_call=(lambda k: INTER if (k + i) % 2 else 0))
+
+
+def test_wavesim_every_golden(wavesim, G):
+    for i, c in enumerate(G):
+        mc.run_golden_case(wavesim, c, fmt_of_call=(lambda k: 0 if (k + i) % 2 else INTER))
+
+
+def test_hostsim_random_family(sim):
+    assert mc.family_check(sim, mc.family(20270, 40)) == 40
+
+
+def test_wavesim_random_family(wavesim):
+    assert mc.family_check(wavesim, mc.family(20271, 13, max_frames=3)) == 13
+
+
+def test_refusals(sim):
+    import lamejs_amd
+    # a gain beyond the bound, a negative scale, a gain that is not finite: lhip_create -3 with a message
+    for kw, pat in (({"scale": 4.5}, "exceed 4"), ({"scale": 2.0, "scale_left": 2.5}, "exceed 4"), ({"scale_right": -4.25}, "exceed 4"), ({"scale": -0.5}, "negative"),
+                    ({"scale_left": float("nan")}, "finite")):
+        with pytest.raises(lamejs_amd.LhipError, match=r"\(-3\).*" + pat):
+            lamejs_amd.Mp3Encoder(2, 44100, 128, lib=sim, **kw)
+    lamejs_amd.Mp3Encoder(2, 44100, 128, lib=sim, scale=4.0).close()                       # at the bound
+    lamejs_amd.Mp3Encoder(1, 44100, 128, lib=sim, scale_right=100.0).close()               # one input channel: scale_right is dead
+    lamejs_amd.Mp3Encoder(2, 44100, 128, lib=sim, downmix=True, scale=4.0, scale_right=4.0).close()      # downmix: scale never reaches the right samples
+    with pytest.raises(TypeError, match="two input channels"):
+        lamejs_amd.Mp3Encoder(1, 44100, 128, lib=sim, downmix=True)
+    with pytest.raises(TypeError, match="joint"):
+        lamejs_amd.Mp3Encoder(2, 44100, 128, lib=sim, downmix=True, joint=True)
+    if NODE:
+        r = subprocess.run([NODE, "-e", "const t = require(process.argv[1]); let n = 0; for (const o of [[1, { downmix: true }], [2, { downmix: true, jointStereo: true }]])"
+                            " try { t.buildBlob(o[0], 44100, 128, o[1]); } catch (e) { if (e instanceof TypeError) n++; } console.log(n);", str(ROOT / "lamejs_amd" / "js" / "tables.js")], capture_output=True, text=True)
+        assert r.stdout.strip() == "2", r.stderr[-1000:]
+    # a downmix blob is a two-channel-input blob: a one-channel lhip_create refuses it
+    blob = lamejs_amd.tables_blob(2, 44100, 128, downmix=True)
+    from lamejs_amd import _Config
+    h = ctypes.c_void_p()
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    assert sim.lhip_create(ctypes.byref(_Config(1, 44100, 128, -1)), buf, len(blob), ctypes.byref(h)) == -4 and b"does not match" in sim.lhip_last_error()
+    # a Float32 sample between the scaled limit (131072 / 4) and 131072: -4, the message names it, nothing is consumed
+    enc, twin = (lamejs_amd.Mp3Encoder(2, 44100, 128, lib=sim, downmix=True, scale_right=4.0) for _ in range(2))
+    rng = np.random.RandomState(5)
+    L, R = (rng.randint(-20000, 20000, 4 * 1152).astype(np.float32) + 0.25 for _ in range(2))
+    a = encode_fmt(sim, enc, F32, L[:1152], R[:1152])
+    assert a == encode_fmt(sim, twin, F32, L[:1152], R[:1152])
+    bad = R[1152:2304].copy()
+    bad[77] = 40000.0
+    for fmt in (F32, F32 | INTER):
+        assert encode_fmt(sim, enc, fmt, L[1152:2304], bad, strict=False) == -4
+        assert b"|x| <= 32768" in sim.lhip_last_error() and b"channel 1, index 77" in sim.lhip_last_error()
+    assert encode_fmt(sim, enc, F32, L[1152:], R[1152:]) + enc.flush() == encode_fmt(sim, twin, F32 | INTER, L[1152:], R[1152:]) + twin.flush()
+    enc.close()
+    twin.close()
+
+
+def test_device_entry_reads_rejected_samples_as_zero_before_gain_and_mix(sim):
+    """The device-pointer entry of the simulation: two out-of-contract Float32 samples in the right channel of a downmix are zeroed and counted
+    (source positions: both source channels are scanned); Int16 formats count nothing."""
+    from pcmformats_cases import sim_device_call
+    assert mc.device_downmix_check(sim, sim_device_call) == 4
+
+
+def test_seek_on_a_downmix_stream(sim, G):
+    """lhip_seek on a downmix stream with gains (both Int16 tails go through the same arithmetic), cut at frame 4 of a 12-frame stream: the
+    state at the cut and the bytes after it equal the unbroken stream's."""
+    import lamejs_amd
+    c = next(x for x in G if x["name"] == "downmix_flip_left_double_right")
+    L, R = mc.case_pcm(c)
+    cutpos, warm = 4 * 1152, 2 * 1152
+    whole, cut = mc.make_encoder(sim, c), mc.make_encoder(sim, c)
+    whole.encodeBuffer(L[:cutpos], R[:cutpos])
+    state_at_cut = whole.state_get()
+    rest = whole.encodeBuffer(L[cutpos:], R[cutpos:]) + whole.flush()
+    nt, p0 = cut.seek_tail_samples(), cutpos - warm
+    with pytest.raises(ValueError, match="both tails"):
+        cut.seek(p0, L[p0 - nt:p0])
+    cut.seek(p0, L[p0 - nt:p0], R[p0 - nt:p0])
+    cut.encodeBuffer(L[p0:cutpos], R[p0:cutpos])          # warm-up frames, output discarded
+    got_state = cut.state_get()
+    if got_state != state_at_cut:
+        from state_fields import describe_diff
+        raise AssertionError(describe_diff(got_state, state_at_cut))
+    assert cut.encodeBuffer(L[cutpos:], R[cutpos:]) + cut.flush() == rest and len(rest) > 7 * 400
+    whole.close()
+    cut.close()
+
+
+def test_state_does_not_depend_on_the_layout_of_the_calls(sim, G):
+    for name in ("downmix_f32", "gains_f32", "downmix_44100_32_resample_int"):
+        c = next(x for x in G if x["name"] == name)
+        L, R = mc.case_pcm(c)
+        ty = F32 if c["kind"] == "f32" else S16
+        a, b = mc.make_encoder(sim, c), mc.make_encoder(sim, c)
+        p, out = 0, [b"", b""]
+        for n in (1152, 777, 2305, 1):
+            out[0] += encode_fmt(sim, a, ty, L[p:p + n], R[p:p + n])
+            out[1] += encode_fmt(sim, b, ty | INTER, L[p:p + n], R[p:p + n])
+            p += n
+        assert out[0] == out[1] and a.state_get() == b.state_get() and len(a.state_get()) == sim.lhip_state_bytes(a._h)
+        a.close()
+        b.close()
+
+
+@pytest.mark.skipif(NODE is None or not (ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node").exists() or not (ROOT / "oracle" / "_ref" / "lame.all.js").exists(),
+                    reason="node / addon / reference bundle not available")
+def test_js_beside_the_live_reference_hostsim():
+    import os
+    env = dict(os.environ, LAMEJS_HIP_LIB=str(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so"))
+    r = subprocess.run([NODE, str(ROOT / "tests" / "js_inputmix_check.js"), "20272"], capture_output=True, text=True, env=env)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    assert res["mismatches"] == 0 and res["calls"] == 137 and res["type_errors"] == 2 and set(res["families"]) >= {"downmix", "downmix_interleaved", "gains", "batch", "pending", "fractional"}
