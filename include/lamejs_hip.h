@@ -48,6 +48,13 @@
  * magnitude; the Float32 sample limit of such a stream is 131072 / max(1, |gain left|, |gain right|).  lhip_seek applies the same arithmetic
  * to its Int16 tails (a downmix stream needs both).
  *
+ * Frame protection and header flags (extension).  A blob built with { protect } (tables.js) carries error_protection = 1 and a sideinfo_len
+ * two bytes above the mode's (Lame.js:1109-1110): every frame then holds a CRC-16 as ISO 11172-3 defines it (polynomial 0x8005, preset
+ * 0xffff, over header bytes 2, 3 and the side information) in bytes 4, 5, computed by the kernels that format frames.  Frame sizes, and
+ * with them lhip_encode_output_bytes and lhip_max_output_bytes, do not change; each frame has 16 bits less for main data.  { copyright,
+ * original, privateBit, emphasis } set the header bits of those names.  lhip_create returns -3 with a message when sideinfo_len does not fit
+ * the flag, for a flag that is not 0 or 1, for emphasis 2 (reserved), and for error_protection on a non-integer-ratio stream.
+ *
  * Semantics preserved: any chunking of the same sample stream yields the same bytes; a call
  * returns the bytes of all whole frames completed by that call (possibly 0); errors are negative
  * return codes mirroring the reference (-1 output buffer too small, -3 bad handle, -4 internal/device
@@ -165,7 +172,10 @@ int lhip_output_bytes_is_exact(const lhip_stream* s);
 /* Batch extension (BASELINE config 5: many independent streams, one launch): stream i receives
  * nsamples[i] samples from left[i]/right[i] and its frames are written to out[i] (capacity
  * out_cap[i]); written[i] receives the byte count or a negative code.  All streams must share one
- * configuration (same tables blob) and device.  Returns 0 or the first negative code. */
+ * device.  Streams of one configuration (same tables blob) share a launch; a batch that mixes table blobs --
+ * protected beside unprotected streams, say -- is launched blob by blob in order of first appearance and
+ * synchronises; a refusal in a later group leaves the earlier groups encoded (written[] says which).
+ * Returns 0 or the first negative code. */
 int lhip_encode_batch(lhip_stream* const* streams, size_t nstreams, const int16_t* const* left,
                       const int16_t* const* right, const size_t* nsamples, uint8_t* const* out,
                       const size_t* out_cap, int64_t* written);

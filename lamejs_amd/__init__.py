@@ -122,7 +122,8 @@ def _gain_text(g) -> str:
 
 
 def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, reservoir: bool = False, fractional_resample: bool = False,
-                downmix: bool = False, scale=None, scale_left=None, scale_right=None) -> bytes:
+                downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False, copyright: bool = False, original: bool = True,
+                private_bit: bool = False, emphasis: int = 0) -> bytes:
     """The LHTB table blob for a configuration.
 
     Built by the host-side JavaScript ``lamejs_amd/js/tables.js`` (so every transcendental comes
@@ -134,7 +135,14 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     ``{ fractionalResample: true }`` of tables.js); for every other configuration the blob is the same with and without it.
     ``downmix`` (two channels in, mono out), ``scale``, ``scale_left``, ``scale_right``: the reference's input gains and downmix
     (``{ downmix, scale, scaleLeft, scaleRight }`` of tables.js); without them the blob is the bytes it always was.
+    ``protect`` (CRC-protected frames), ``copyright``, ``original``, ``private_bit``, ``emphasis`` (0, 1 or 3): the frame header's settings
+    (``{ protect, copyright, original, privateBit, emphasis }`` of tables.js); at their defaults the blob is the bytes it always was.
     """
+    for name, v in (("protect", protect), ("copyright", copyright), ("original", original), ("private_bit", private_bit)):
+        if v not in (True, False, 0, 1):
+            raise ValueError(f"{name} must be True or False")
+    if isinstance(emphasis, bool) or emphasis not in (0, 1, 3):
+        raise ValueError("emphasis must be 0 (none), 1 (50/15 us) or 3 (CCITT J.17); 2 is reserved")
     if downmix and channels != 2:
         raise TypeError("downmix needs two input channels")
     if downmix and joint:
@@ -142,6 +150,7 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     joint = bool(joint) and channels == 2
     frac = bool(fractional_resample)
     mix = (["downmix"] if downmix else []) + [f"{k}={_gain_text(v)}" for k, v in (("scale", scale), ("scaleLeft", scale_left), ("scaleRight", scale_right)) if v is not None]
+    mix += (["protect"] if protect else []) + (["copyright"] if copyright else []) + ([] if original else ["original=0"]) + (["privateBit"] if private_bit else []) + ([f"emphasis={int(emphasis)}"] if emphasis else [])
     f = _TABLE_DIR / f"t_{channels}_{samplerate}_{kbps}{'_joint' if joint else ''}{'_resv' if reservoir else ''}{'_frac' if frac else ''}{''.join('_' + m.replace('=', '') for m in mix)}.bin"
     if not f.exists() or not blob_is_current(f.read_bytes()):      # a cached blob made by another version of its generator is stale
         _TABLE_DIR.mkdir(exist_ok=True)
@@ -187,7 +196,8 @@ class Mp3Encoder:
     """Mirror of the reference's ``Mp3Encoder`` (index.js:66-136)."""
 
     def __init__(self, channels: int = 1, samplerate: int = 44100, kbps: int = 128, device: int = -1, lib=None, joint: bool = False, reservoir: bool = False,
-                 fractional_resample: bool = False, downmix: bool = False, scale=None, scale_left=None, scale_right=None):
+                 fractional_resample: bool = False, downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False,
+                 copyright: bool = False, original: bool = True, private_bit: bool = False, emphasis: int = 0):
         """``joint`` (extension, not in the reference's wrapper): encode two channels in the reference's joint-stereo mode --
         per frame mid/side or left/right, as its encoder core decides when asked for MPEGMode.JOINT_STEREO.
         ``reservoir`` (extension): encode with the bit reservoir in use (the reference's wrapper disables it, index.js:108); the frames
@@ -199,11 +209,15 @@ class Mp3Encoder:
         ``downmix`` (extension, two channels): the reference's MPEGMode.MONO for two input channels -- ``encodeBuffer(l, r)`` and
         ``encode_interleaved`` take both channels, the stream is a mono stream of ``0.5 * (l + r)`` mixed where the samples are read.
         ``scale``, ``scale_left``, ``scale_right`` (extension): the reference's ``gfp.scale`` (replaces the preset's) and per-channel
-        gains, applied in its order and with its roundings (include/lamejs_hip.h, "Input gains and downmix")."""
+        gains, applied in its order and with its roundings (include/lamejs_hip.h, "Input gains and downmix").
+        ``protect`` (extension): CRC-protected frames, the reference core's ``gfp.error_protection`` (LAME's ``-p``) -- the same frame sizes,
+        two more bytes of side information and so 16 bits less main data per frame.  ``copyright``, ``original``, ``private_bit``,
+        ``emphasis`` (0, 1 or 3; 2 is reserved): the header bits of those names.  A value outside these raises ``ValueError``."""
         self._lib = lib or load_library()
         self.channels, self.samplerate, self.kbps = int(channels), int(samplerate), int(kbps)
         self._resv = bool(reservoir)
-        blob = tables_blob(self.channels, self.samplerate, self.kbps, joint, reservoir, fractional_resample, downmix, scale, scale_left, scale_right)
+        blob = tables_blob(self.channels, self.samplerate, self.kbps, joint, reservoir, fractional_resample, downmix, scale, scale_left, scale_right,
+                           protect, copyright, original, private_bit, emphasis)
         cfg = _Config(self.channels, self.samplerate, self.kbps, device)
         h = ctypes.c_void_p()
         buf = ctypes.create_string_buffer(blob, len(blob))

@@ -145,6 +145,48 @@ LHIP_DEV void side_field(const GrSide& gi, int f, int GR, uint32_t* v, int* n) {
     }
     *v = (uint32_t)val; *n = w;
 }
+// ---- frame protection (extension { protect }; BitStream.js:233-257, 283-285, 406-409): the CRC-16 of ISO 11172-3 -- polynomial x^16 + x^15 + x^2 + 1,
+// register preset to 0xffff, bits MSB first -- over header bytes 2, 3 and the side information (bytes 6 .. sideinfo_len - 1), stored in bytes 4, 5.
+// A CRC is linear over GF(2): with n message bytes m[0 .. n-1] the register ends as  0xffff x^(8n) + sum m[i] x^(8 (n + 1 - i))  mod the polynomial.
+// One lane per byte forms its term -- one 16-step product with a constant power of x --, one more lane the preset's, an XOR over the wave adds them:
+// 16 dependent steps and a reduction instead of 8 n <= 272 steps on one lane (the packer sits on the serial chain of the one-frame call and of the reservoir walk).
+enum { CRC16_POLY = 0x18005, CRC16_MAXMSG = 34 };                 // the largest message: 2 + (38 - 6) bytes
+struct Crc16Pow { uint16_t v[CRC16_MAXMSG + 2]; };              // v[k] = x^(8 k) mod the polynomial
+constexpr Crc16Pow crc16_pow() {
+    Crc16Pow t{};
+    uint32_t r = 1;
+    for (int k = 0; k < CRC16_MAXMSG + 2; k++) {
+        t.v[k] = (uint16_t)r;
+        for (int b = 0; b < 8; b++) { r <<= 1; if (r & 0x10000) r ^= CRC16_POLY; }
+    }
+    return t;
+}
+// a * b mod the polynomial (a, b < 2^16)
+LHIP_DEV uint32_t crc16_mul(uint32_t a, uint32_t b) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int i = 15; i >= 0; i--) {
+        r <<= 1;
+        if (r & 0x10000) r ^= CRC16_POLY;
+        if ((b >> i) & 1) r ^= a;
+    }
+    return r;
+}
+// header + side information are complete in w (bytes 4, 5 still zero); called by all lanes of the wave that wrote them
+LHIP_DEV void bits_crc(uint32_t* w, int sideinfo_len, int lane) {
+    constexpr Crc16Pow pw = crc16_pow();
+    wave_sync();                                                 // the side information came from all lanes
+    const int n = sideinfo_len - 4;                              // lhip_create: 13 <= sideinfo_len <= 38
+    uint32_t c = 0;
+    for (int i = lane; i <= n; i += LHIP_NL) {                   // (one trip on the device; the one-lane simulation walks the bytes)
+        uint32_t a = 0xffff;
+        int e = n;
+        if (i < n) { const int bi = i < 2 ? i + 2 : i + 4; a = (w[bi >> 2] >> (24 - 8 * (bi & 3))) & 0xff; e = n + 1 - i; }
+        c ^= crc16_mul(a, pw.v[e]);
+    }
+    c = (uint32_t)wave_xor((int)c);
+    if (lane == 0) put_bits(w, 32, c, 16);
+}
 // the header part is written by lane 0 only; everybody continues from where it stopped
 LHIP_DEV int uni_bits_pos(int pos) { return wave_bcast(pos, 0); }
 
@@ -229,6 +271,7 @@ LHIP_DEV void bits_header(const Tables& T, const Workspace& W, const BitsFrame& 
         PUT(T.bitrate_index, 4) PUT(T.samplerate_index, 2) PUT(padding, 1) PUT(T.extension, 1)
         PUT(T.mode, 2) PUT(T.mode == 1 ? side[0].mode_ext : 0, 2)                  // mode_ext: the frame's M/S decision in joint stereo (BitStream.js:279)
         PUT(T.copyright, 1) PUT(T.original, 1) PUT(T.emphasis, 2)
+        pos += T.error_protection ? 16 : 0;                                        // sixteen zero bits: the CRC's place (BitStream.js:283-285; the image is zero there), filled in below
         const int mdb = resv ? js_toint32(W.fr[F.fidx].main_data_begin) : 0;       // writeheader shifts the number: ToInt32 of a possibly fractional value
         if (GR == 2) {
             PUT(mdb, 9)
@@ -255,6 +298,7 @@ LHIP_DEV void bits_header(const Tables& T, const Workspace& W, const BitsFrame& 
         put_bits(w, pos + off, v, n);
         pos += tot;
     }
+    if (T.error_protection) bits_crc(w, T.sideinfo_len, lane);                         // before the header is emitted or queued (wave-uniform; the one branch an unprotected stream sees)
 }
 // main data of one granule-channel (scalefactors + Huffman data, BitStream.js:600-689) from bit `pos` of w; qbuf: 288 words of this wave's LDS.  Returns the
 // position behind it (pos + part2_length + part2_3_length of the record: what the side info announces)

@@ -992,7 +992,7 @@ struct TableSet {
     void* d_qtabs = nullptr;
     int device = 0;
     int base_frame_bytes = 0;
-    bool bad_gain = false;  // build_tables refused the blob's input gains (lhip_create: -3)
+    bool bad_option = false;  // build_tables refused an option of the blob -- input gains, frame protection, header flags (lhip_create: -3)
     ~TableSet() { rt::dfree(d_blob); rt::dfree(d_extra); rt::dfree(d_qtabs); }
 };
 
@@ -1100,12 +1100,12 @@ static bool build_tables(TableSet& ts, const void* blob, size_t nbytes, const lh
         T.do_scale = T.do_scale != 0; T.do_scale_left = T.do_scale_left != 0; T.do_scale_right = T.do_scale_right != 0;
         if (T.channels_in == 1) T.do_scale_right = 0;                       // one input channel: scale_right is dead
         const bool down = T.channels_in == 2 && T.channels_out == 1;
-        if (!std::isfinite(T.scale) || !std::isfinite(T.scale_left) || !std::isfinite(T.scale_right)) { set_err("input gains: scale, scale_left and scale_right must be finite"); ts.bad_gain = true; return false; }
-        if (T.scale < 0) { set_err("input gains: scale must not be negative (the reference asserts scale >= 0)"); ts.bad_gain = true; return false; }
+        if (!std::isfinite(T.scale) || !std::isfinite(T.scale_left) || !std::isfinite(T.scale_right)) { set_err("input gains: scale, scale_left and scale_right must be finite"); ts.bad_option = true; return false; }
+        if (T.scale < 0) { set_err("input gains: scale must not be negative (the reference asserts scale >= 0)"); ts.bad_option = true; return false; }
         const double gl = (T.do_scale ? T.scale : 1.0) * (T.do_scale_left ? T.scale_left : 1.0);
         const double gr = ((T.do_scale && !down) ? T.scale : 1.0) * (T.do_scale_right ? T.scale_right : 1.0);     // the reference's downmix exception: `scale` never reaches the right samples
         const double g = fmax(1.0, fmax(fabs(gl), fabs(gr)));
-        if (g > 4.0) { set_err("input gains: the combined gain of a channel must not exceed 4 in magnitude (Int16 full scale then ends exactly at the sample limit, 131072)"); ts.bad_gain = true; return false; }
+        if (g > 4.0) { set_err("input gains: the combined gain of a channel must not exceed 4 in magnitude (Int16 full scale then ends exactly at the sample limit, 131072)"); ts.bad_option = true; return false; }
         T.pcm_limit = (float)((double)PCM_F32_LIMIT / g);
         T.in_mix = down ? 2 : ((T.do_scale_left || T.do_scale_right) ? 1 : 0);
     }
@@ -1124,9 +1124,22 @@ static bool build_tables(TableSet& ts, const void* blob, size_t nbytes, const lh
             set_err("configuration outside the supported envelope (resampling by a non-integer ratio)"); return false;
         } else T.rs_ratio = r;
     }
-    if ((T.version != 1 && T.version != 0) || T.mode_gr != (T.version == 1 ? 2 : 1) || T.quant_comp != 9 || T.quant_comp_short != 9 || T.error_protection || T.sfb21_extra ||
+    if ((T.version != 1 && T.version != 0) || T.mode_gr != (T.version == 1 ? 2 : 1) || T.quant_comp != 9 || T.quant_comp_short != 9 || T.sfb21_extra ||
         T.substep_shaping != 0 || T.noise_shaping_amp > 2 || T.use_best_huffman > 1 || T.athaa_loudapprox != 2 || T.full_outer_loop != 0) {
         set_err("configuration outside the supported envelope (MPEG-1/2/2.5 CBR, quality-3 switches)"); return false;
+    }
+    // frame protection and header flags (extension { protect, copyright, original, privateBit, emphasis }): the side information of a protected stream is
+    // two bytes longer (Lame.js:1109-1110) -- every budget reads sideinfo_len, so it must be the mode's value plus exactly what the flag says
+    {
+        const int base = T.version == 1 ? (T.channels_out == 1 ? 4 + 17 : 4 + 32) : (T.channels_out == 1 ? 4 + 9 : 4 + 17);
+        if ((T.error_protection != 0 && T.error_protection != 1) || T.sideinfo_len != base + 2 * T.error_protection) {
+            set_err("frame protection: sideinfo_len must be the mode's " + std::to_string(base) + " bytes, plus 2 exactly when error_protection is set"); ts.bad_option = true; return false;
+        }
+        if ((T.copyright & ~1) || (T.original & ~1) || (T.extension & ~1) || !(T.emphasis == 0 || T.emphasis == 1 || T.emphasis == 3)) {
+            set_err("header flags: copyright, original and extension are 0 or 1, emphasis is 0, 1 or 3 (2 is reserved)"); ts.bad_option = true; return false;
+        }
+        // the stand-in frames of a non-integer-ratio stream's flush are written by the host without a CRC of their own
+        if (T.error_protection && T.rs_frac) { set_err("frame protection cannot be combined with fractionalResample (the flush's stand-in frames carry no pinned CRC)"); ts.bad_option = true; return false; }
     }
     // ---- derived index tables ----
     const int32_t* h_s3ind = (const int32_t*)host_arr("s3ind");
@@ -2064,7 +2077,7 @@ int lhip_create(const lhip_config* cfg, const void* tables, size_t tables_bytes,
     } else {
         ts = std::make_shared<TableSet>();
         ts->device = dev;
-        if (!build_tables(*ts, tables, tables_bytes, *cfg, ctx->stream)) return ts->bad_gain ? -3 : LHIP_ERR_INTERNAL;      // (-3: a gain outside the contract, with a message)
+        if (!build_tables(*ts, tables, tables_bytes, *cfg, ctx->stream)) return ts->bad_option ? -3 : LHIP_ERR_INTERNAL;      // (-3: an option's value outside the contract, with a message)
         ctx->tables[key] = ts;
     }
     std::unique_ptr<lhip_stream> s(new lhip_stream());
@@ -2142,12 +2155,13 @@ static int encode_many(lhip_stream* const* streams, size_t n, int format, const 
     // (g_resv_stream); a stream that ends with this call (flush) has its bitstream padded by the same launch -- decided per stream
     // (an already flushed stream in a flush batch has nothing to encode and is not flushed again).  The byte counts are only known
     // on the device, so these calls always synchronise.
-    const Tables& T0 = streams[0]->ts->T;
-    const bool resv = !T0.disable_reservoir;
-    if (resv) for (size_t i = 0; i < n; i++) jobs[i].flush = flush_stream && ns[i] > 0;
+    bool resv = false;
+    for (size_t i = 0; i < n; i++) if (!streams[i]->ts->T.disable_reservoir) { resv = true; jobs[i].flush = flush_stream && ns[i] > 0; }
     // Non-integer-ratio streams (extension { fractionalResample }): a call the reference would not consume whole is refused before anything is
     // consumed on ANY stream of the batch.  Their batches may mix configurations (a caller with many low-bitrate streams has one frame per
     // stream and call at most): the streams are then launched configuration by configuration, in order of first appearance.
+    // So is any other batch whose streams do not share one table blob (protected beside unprotected streams, say): a launch works with one table set.
+    // Such a call synchronises, and a refusal in a later group leaves the earlier groups encoded -- written[] says which.
     bool any_frac = false, mixed = false;
     for (size_t i = 0; i < n; i++) { any_frac |= streams[i]->ts->T.rs_frac != 0; mixed |= streams[i]->ts.get() != streams[0]->ts.get(); }
     if (any_frac) {
@@ -2157,6 +2171,8 @@ static int encode_many(lhip_stream* const* streams, size_t n, int format, const 
                 for (size_t k = 0; k < n; k++) if (written) written[k] = LHIP_ERR_INTERNAL;
                 return LHIP_ERR_INTERNAL;
             }
+    }
+    {
         if (mixed) {
             std::vector<char> done(n, 0);
             for (size_t i = 0; i < n; i++) {

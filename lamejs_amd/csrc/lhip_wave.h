@@ -15,6 +15,7 @@ template <int N> LHIP_DEV void wave_max_n(int (&v)[N]) { (void)v; }
 LHIP_DEV int wave_max(int v) { return v; }
 LHIP_DEV int wave_min(int v) { return v; }
 LHIP_DEV int wave_or(int v) { return v; }
+LHIP_DEV int wave_xor(int v) { return v; }
 LHIP_DEV uint64_t wave_or64(uint64_t v) { return v; }
 LHIP_DEV float wave_maxf(float v) { return v; }
 LHIP_DEV float wave_maxf_pos(float v) { return v; }
@@ -181,6 +182,7 @@ template <int N> LHIP_DEV void wave_sum_n(int (&v)[N]) { for (int i = 0; i < N; 
 template <int N> LHIP_DEV void wave_max_n(int (&v)[N]) { for (int i = 0; i < N; i++) v[i] = wave_max(v[i]); }
 LHIP_DEV int wave_min(int v) { uint64_t a[64]; wsim::exchange(4, (uint64_t)(uint32_t)v, a); int m = (int)(uint32_t)a[0]; for (int l = 1; l < 64; l++) if ((int)(uint32_t)a[l] < m) m = (int)(uint32_t)a[l]; return m; }
 LHIP_DEV int wave_or(int v) { uint64_t a[64]; wsim::exchange(5, (uint64_t)(uint32_t)v, a); uint32_t m = 0; for (int l = 0; l < 64; l++) m |= (uint32_t)a[l]; return (int)m; }
+LHIP_DEV int wave_xor(int v) { uint64_t a[64]; wsim::exchange(16, (uint64_t)(uint32_t)v, a); uint32_t m = 0; for (int l = 0; l < 64; l++) m ^= (uint32_t)a[l]; return (int)m; }
 LHIP_DEV uint64_t wave_or64(uint64_t v) { uint64_t a[64]; wsim::exchange(6, v, a); uint64_t m = 0; for (int l = 0; l < 64; l++) m |= a[l]; return m; }
 LHIP_DEV float wave_maxf(float v) { uint64_t a[64]; wsim::exchange(7, wsim::bits_of(v), a); float m = wsim::from_bits<float>(a[0]); for (int l = 1; l < 64; l++) { const float x = wsim::from_bits<float>(a[l]); if (x > m) m = x; } return m; }
 LHIP_DEV float wave_maxf_pos(float v) { return wave_maxf(v); }
@@ -259,6 +261,7 @@ LHIP_DEV int dpp_op_add(int a, int b) { return a + b; }
 LHIP_DEV int dpp_op_max(int a, int b) { return a > b ? a : b; }
 LHIP_DEV int dpp_op_min(int a, int b) { return a < b ? a : b; }
 LHIP_DEV int dpp_op_or(int a, int b) { return a | b; }
+LHIP_DEV int dpp_op_xor(int a, int b) { return a ^ b; }
 // N independent reductions side by side: step s of every value before step s + 1 of any, so that the two wait states a DPP read
 // needs after the VALU write of its source are filled by the other chains instead of s_nop (which costs an issue slot like any
 // other instruction).
@@ -276,6 +279,7 @@ LHIP_DEV int wave_sum(int v) { LHIP_DPP_REDUCE(dpp_op_add, 0) }
 LHIP_DEV int wave_max(int v) { LHIP_DPP_REDUCE(dpp_op_max, (int)0x80000000) }
 LHIP_DEV int wave_min(int v) { LHIP_DPP_REDUCE(dpp_op_min, 0x7fffffff) }
 LHIP_DEV int wave_or(int v) { LHIP_DPP_REDUCE(dpp_op_or, 0) }
+LHIP_DEV int wave_xor(int v) { LHIP_DPP_REDUCE(dpp_op_xor, 0) }
 LHIP_DEV uint64_t wave_or64(uint64_t v) {
     const unsigned lo = (unsigned)wave_or((int)(unsigned)v), hi = (unsigned)wave_or((int)(unsigned)(v >> 32));
     return ((uint64_t)hi << 32) | lo;

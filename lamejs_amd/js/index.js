@@ -26,6 +26,11 @@
  * the samples are read on the device; byte for byte what the reference's core gives for MPEGMode.MONO with those gains.  `scale` replaces the
  * preset's (0.95 at and below 128 kbps).  { downmix } with one channel or with { jointStereo } is a TypeError; a gain beyond 4 in magnitude,
  * a negative scale or a gain that is not finite is refused at construction.
+ * Extension { protect, copyright, original, privateBit, emphasis }: the frame header's settings, which the reference's wrapper leaves at their defaults.
+ * new Mp3Encoder(2, 44100, 128, { protect: true }) writes CRC-protected frames (LAME's -p): the reference core's bytes for gfp.error_protection = 1 --
+ * same frame sizes, two more bytes of side information per frame, a CRC-16 as ISO 11172-3 defines it.  copyright: true, original: false,
+ * privateBit: true and emphasis: 0 | 1 | 3 set the header bits of those names; any other value (emphasis 2 is reserved) is a RangeError.  Accepted
+ * wherever { downmix } is, encodeBatch() of protected and unprotected encoders included; not with a { fractionalResample } stream that resamples.
  * Extension { fractionalResample: true }: the 49 (channels, sample rate, kbps) triples the reference resamples by a non-integer ratio -- refused
  * by default, because the reference feeds itself NaN samples there once a call is long enough -- are accepted as call-sequence streams: every
  * encodeBuffer() gives the reference's bytes for the same sequence of call lengths; a call longer than the reference consumes whole throws
@@ -57,7 +62,8 @@ function loadAddon() {
 const blobCache = new Map();
 function tablesBlob(channels, samplerate, kbps, opts) {
     const key = [channels, samplerate, kbps, opts && opts.jointStereo ? 1 : 0, opts && opts.reservoir ? 1 : 0, opts && opts.fractionalResample ? 1 : 0,
-        opts && opts.downmix ? 1 : 0, opts ? String(opts.scale) : '', opts ? String(opts.scaleLeft) : '', opts ? String(opts.scaleRight) : ''].join('|');     /* (pendingFrames is host-side only) */
+        opts && opts.downmix ? 1 : 0, opts ? String(opts.scale) : '', opts ? String(opts.scaleLeft) : '', opts ? String(opts.scaleRight) : '',
+        opts ? ['protect', 'copyright', 'original', 'privateBit', 'emphasis'].map((k) => String(opts[k])).join(',') : ''].join('|');     /* (pendingFrames is host-side only) */
     let blob = blobCache.get(key);
     if (!blob) { blob = tables.buildBlob(channels, samplerate, kbps, opts).blob; blobCache.set(key, blob); }
     return blob;
@@ -194,7 +200,8 @@ module.exports.deviceCount = function () { return loadAddon().deviceCount(); };
  *                                         holds channels * n samples (L R L R ...), rights is ignored
  *   flushBatch(encoders)                  likewise for flush()
  *   setDevices(mask)                      let the library deal new encoders round-robin over the GPUs named by the bit mask
- * The encoders of one call must share (channels, samplerate, kbps) and the device ({ fractionalResample } streams: the device only).
+ * The encoders of one call must share the channel count and the device; encoders of one configuration share a launch, other configurations and
+ * options (protected beside unprotected encoders, say) get a launch each inside the same call.
  */
 module.exports.setDevice = function (d) { defaultDevice = d | 0; };
 /* setDevices(mask): bit d = HIP device d may be used; encoders constructed with the default device (-1) are then dealt round-robin

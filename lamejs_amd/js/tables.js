@@ -216,6 +216,31 @@ function resolveParams(channels, samplerate, kbps, opts) {
     /* Lame.js:1103-1110 */
     if (p.version == 1) p.sideinfo_len = (p.channels_out == 1) ? 4 + 17 : 4 + 32;
     else p.sideinfo_len = (p.channels_out == 1) ? 4 + 9 : 4 + 17;
+    /* extension { protect, copyright, original, privateBit, emphasis }: gfp.error_protection (LAME's -p) and the header's flag bits
+     * (BitStream.js:273-285), which the reference's wrapper leaves at lame_init's values.  A protected frame carries a CRC-16 behind the header:
+     * two more bytes of side information (Lame.js:1109-1110), so 16 bits less for every frame's main data.  emphasis 2 is reserved. */
+    {
+        const given = (k) => !!opts && opts[k] !== undefined && opts[k] !== null;
+        const flag = (k, dflt) => {
+            if (!given(k)) return dflt;
+            const v = opts[k];
+            if (v !== true && v !== false && v !== 0 && v !== 1) throw new RangeError('lamejs_amd: { ' + k + ' } must be true or false');
+            return v ? 1 : 0;
+        };
+        p.error_protection = flag('protect', 0);
+        p.copyright = flag('copyright', 0);
+        p.original = flag('original', 1);                    /* lame_init_old: original = 1 */
+        p.extension = flag('privateBit', 0);
+        p.emphasis = 0;
+        if (given('emphasis')) {
+            if (opts.emphasis !== 0 && opts.emphasis !== 1 && opts.emphasis !== 3) throw new RangeError('lamejs_amd: { emphasis } must be 0 (none), 1 (50/15 us) or 3 (CCITT J.17); 2 is reserved');
+            p.emphasis = opts.emphasis;
+        }
+        if (p.error_protection) {
+            if (p.rs_filter_l == 31) throw new Error('lamejs_amd: { protect } and { fractionalResample } cannot be combined for (' + channels + ',' + samplerate + ',' + kbps + ')');
+            p.sideinfo_len += 2;
+        }
+    }
 
     /* CBR: ABR preset row for this bitrate (Lame.js:1202-1230, Presets.js:270-357) */
     const row = C.abr_switch_map[nearestBitrateFullIndex(brate)];
@@ -280,8 +305,6 @@ function resolveParams(channels, samplerate, kbps, opts) {
     p.useTemporal = 1;
     p.frac_SpF = (((p.version + 1) * 72000 * brate) % out_samplerate) | 0;
 
-    /* header constants (LameGlobalFlags defaults + lame_init_old: original=1) */
-    p.copyright = 0; p.original = 1; p.emphasis = 0; p.extension = 0; p.error_protection = 0;
     return p;
 }
 
@@ -710,11 +733,14 @@ function fractionalCallLimit(p) {
 module.exports = { buildBlob, resolveParams, buildTables, packBlob, sourceHash, fractionalCallLimit };
 
 if (require.main === module) {
-    /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] [fracresample] [downmix] [scale=G] [scaleLeft=G] [scaleRight=G] */
+    /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] [fracresample] [downmix] [scale=G] [scaleLeft=G] [scaleRight=G]
+     *      [protect] [copyright] [original=0|1] [privateBit] [emphasis=E] */
     const [ch, sr, kb, out] = process.argv.slice(2), flags = process.argv.slice(6);
     const opts = { jointStereo: flags.includes('joint'), reservoir: flags.includes('reservoir'), fractionalResample: flags.includes('fracresample') };
     if (flags.includes('downmix')) opts.downmix = true;
     for (const f of flags) { const m = /^(scale|scaleLeft|scaleRight)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
+    for (const k of ['protect', 'copyright', 'privateBit']) if (flags.includes(k)) opts[k] = true;
+    for (const f of flags) { const m = /^(original|emphasis)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
     const r = buildBlob(+ch, +sr, +kb, opts);
     require('fs').writeFileSync(out, r.blob);
     console.log('wrote', out, r.blob.length, 'bytes');
