@@ -1,4 +1,4 @@
-// k_quant_tail.h -- how a launch of the persistent quantization kernel ends (g_quant, lhip_api.cpp).
+// k_quant_tail.h -- how a launch of the persistent quantization kernel ends (g_quant, lhip_kernels.h).
 //
 // What it is for: a launch of the persistent quantization kernel ends with ~2 ms in which waves leave one by one (a two-channel frame is
 // 1.5-2 ms of one wave; measured: 1.29 ms of idle per wave and launch, profiles/r03_quant_wave_tail.txt).  Here a wave that finds the frame

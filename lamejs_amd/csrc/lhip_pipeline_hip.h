@@ -1,0 +1,137 @@
+// lhip_pipeline_hip.h -- run_pipeline of the product: the HIP launch sequence of one batch on the context's stream, and what only a device
+// build has around it (kernel timing, repair statistics left on the device).  Exactly one of this and lhip_pipeline_sim.h is included (lhip_batch.h).
+// Part of lhip_api.cpp's one translation unit (included there, in the order the definitions need).
+#pragma once
+static inline bool g_kt_on_() { return g_kt_on; }
+static_assert(FX_STATS_OFF == FX_STATS * 4, "counter block layout");
+static bool collect_kernel_times(void* st) { if (g_kt_on) { if (!rt::sync(st)) return false; kt_collect(); } return true; }
+// (an asynchronous batch leaves its repair statistics on the device: lhip_last_batch_stats fetches them)
+static bool collect_repair_stats(Context* ctx, BatchPlan& P, bool fetch_fx, const int32_t* fx) {
+    g_stat_pending = nullptr;
+    if (fetch_fx) {
+        P.repaired = fx[0]; P.iters = fx[1];
+        if (fx[2]) { set_err("seed-chain repair did not converge"); return false; }
+    } else if (P.nfr > 0) g_stat_pending = ctx;
+    return true;
+}
+static bool run_pipeline(Context* ctx, BatchPlan& P) {
+    const TableSet& ts = *P.ts; const Tables& T = ts.T; Workspace& W = P.W; const std::vector<StreamDesc>& sd = P.sd;
+    const StreamDesc* dSD = P.dSD; const StreamIO* dIO = P.dIO;
+    const int S = P.S, C = T.channels_out, ngs = P.ngs, nfs = P.nfs, nfr = P.nfr; const bool resv = P.resv, use_frame = P.use_frame;
+    WorkSet& ws = ctx->ws; void* st = ctx->stream; const int64_t in_total = P.in_total;
+    if (P.count_rej) {
+        if (!ws.rejected.ensure(64) || !rt::dzero(ws.rejected.p, 8, st)) return false;
+        int64_t nb = (in_total + 255) / 256;
+        if (nb > 2048) nb = 2048;
+        if (nb < 1) nb = 1;
+        LAUNCHB(KT_COUNT, g_count_rejected, (int)nb, 256, st, dIO, S, T.channels_in, T.pcm_limit, (unsigned long long*)ws.rejected.p);
+        g_rej_pending = ctx;
+    }
+    if (use_frame) {
+        QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;
+        if (resv) LAUNCHB(KT_QUANT, g_frame<1>, S, 64 * FR_WAVES, st, qa, dIO); else LAUNCHB(KT_QUANT, g_frame<0>, S, 64 * FR_WAVES, st, qa, dIO);
+        if (resv) { bool any_flush = false; for (int i = 0; i < S; i++) any_flush |= sd[i].flush != 0; if (any_flush) LAUNCH(KT_BITS, g_resv_flush, S, st, T, W, dSD); }
+    } else {
+    LAUNCH(KT_LOAD, g_load, S, st, T, W, dSD, dIO);
+    if (T.rs_ratio != 1) {          // only the resampler materialises samples; otherwise the consumers convert the caller's Int16 themselves
+        int64_t nb = (in_total / C + 255) / 256;
+        if (nb > 8192) nb = 8192;
+        if (nb < 1) nb = 1;
+        LAUNCHB(KT_PREP, g_prep, (int)nb, 256, st, T, W, dSD, dIO, S);
+    }
+    LAUNCHB(KT_PSYA, g_psyA, XCD_GRID_W(ngs * C), 64 * WPB, st, T, W, dSD, dIO, 0, C);
+    if (T.psy_channels == 4) LAUNCHB(KT_PSYA, g_psyA, XCD_GRID_W(ngs * 2), 64 * WPB, st, T, W, dSD, dIO, 2, 2);
+    LAUNCH(KT_SCAN, g_scan_raw, (ngs + 63) / 64, st, T, W, dSD, ngs);
+    LAUNCH(KT_SCAN, g_scan_attack, (ngs + 63) / 64, st, T, W, dSD, ngs);
+    LAUNCH(KT_SCAN, g_scan_blocktype, (ngs + 63) / 64, st, T, W, dSD, ngs);
+    // g_scan_ath (needs psyA's loudness, feeds psyB and the quantizer) is one workgroup per stream: it runs on a side
+    // stream while polyphase + MDCT (which need neither) keep the chip busy.  With per-kernel timing on, everything stays
+    // on the launch stream so that the HIP events bracket each kernel.
+    bool forked = false;
+    struct AuxJoin {           // an error return between fork and join must not leave g_scan_ath running on the shared workspace
+        void* aux = nullptr;
+        ~AuxJoin() { if (aux) (void)hipStreamSynchronize((hipStream_t)aux); }
+    } aux_guard;
+    if (!g_kt_on) {
+        if (!ws.aux_stream) {
+            hipStream_t a; hipEvent_t e1, e2;
+            if (hipStreamCreateWithFlags(&a, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess &&
+                hipEventCreateWithFlags(&e2, hipEventDisableTiming) == hipSuccess) { ws.aux_stream = a; ws.ev_fork = e1; ws.ev_join = e2; }
+        }
+        if (ws.aux_stream && hipEventRecord((hipEvent_t)ws.ev_fork, (hipStream_t)st) == hipSuccess &&
+            hipStreamWaitEvent((hipStream_t)ws.aux_stream, (hipEvent_t)ws.ev_fork, 0) == hipSuccess) {
+            LAUNCHB(KT_SCAN, g_scan_ath, S, ATH_NT, ws.aux_stream, T, W, dSD);
+            aux_guard.aux = ws.aux_stream;
+            HIPCK(hipEventRecord((hipEvent_t)ws.ev_join, (hipStream_t)ws.aux_stream));
+            forked = true;
+        }
+    }
+    if (!forked) LAUNCHB(KT_SCAN, g_scan_ath, S, ATH_NT, st, T, W, dSD);
+    LAUNCH(KT_POLY, g_poly, XCD_GRID((ngs * C + POLY_PER_WAVE - 1) / POLY_PER_WAVE), st, T, W, dSD, dIO, ngs * C);
+    LAUNCH(KT_MDCT, g_mdct, XCD_GRID(ngs), st, T, W, dSD);
+    if (forked) { HIPCK(hipStreamWaitEvent((hipStream_t)st, (hipEvent_t)ws.ev_join, 0)); aux_guard.aux = nullptr; }
+    if (resv) {
+        // bit reservoir: psyB -> quantization -> bit packing of a stream's frames are a serial chain: one workgroup per stream walks them
+        // (qa.ctr = 1: the idle waves of a workgroup count for the quantizing ones -- only while every workgroup has a CU to itself: with two
+        //  per CU a helper shares its SIMD with the other workgroup's searching wave and the speculative work costs more than it hides --
+        //  512 streams: 2.37 M frames/s without helpers, 2.21 M with, profiles/r05_pass4_* / r05_pass5_*)
+        QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 2; qa.nfs = nfs; qa.ctr = S <= ctx->num_cus ? 1 : 0;
+        LAUNCHB(KT_QUANT, g_resv_stream, S, 64 * RS_WAVES, st, qa);
+    } else {
+    if (T.psy_channels == 4) LAUNCHB(KT_PSYB, g_psyB<4>, XCD_GRID_W(ngs), 64 * WPB, st, T, ts.pb10, W, dSD, -1);
+    else LAUNCHB(KT_PSYB, g_psyB<2>, XCD_GRID_W(ngs), 64 * WPB, st, T, ts.pb10, W, dSD, -1);
+    // persistent quantization kernels: as many workgroups as can be resident (2 per CU), frames dispensed dynamically
+    int qgrid = (nfs + QWAVES - 1) / QWAVES;
+    if (qgrid > ctx->num_cus * 2) qgrid = ctx->num_cus * 2;
+#ifdef LHIP_PHASE_PROF
+    const bool pair = false;
+#else
+    // Two waves per frame while that still leaves SIMDs under-subscribed.  Measured on MI355X (stereo 128 kbps, ms per batch,
+    // persistent / pair): 600 frames 3.40 / 2.20, 1000: 3.52 / 2.41, 2000: 3.66 / 3.61, 4000: 4.82 / 5.15 -> cross-over at
+    // about 2000 frames = 8 x CUs; LAMEJS_HIP_PAIR_MAX_FRAMES overrides the threshold for experiments.
+    static const int pair_max = []() { const char* e = getenv("LAMEJS_HIP_PAIR_MAX_FRAMES"); return e ? atoi(e) : -1; }();
+    const bool pair = (C == 2 && nfs <= (pair_max >= 0 ? pair_max : 6 * ctx->num_cus));
+#endif
+    { QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;
+      if (pair) LAUNCHB(KT_QUANT, g_quant_pair<0>, nfs, 128, st, qa); else LAUNCHB(KT_QUANT, g_quant<0>, qgrid, 64 * QWAVES, st, qa); }
+    if (nfr > 0) {
+        // validation of the seed chain + repair of the flagged frames, decided on the device (no host round trip in the pipeline)
+        QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 1; qa.nfs = nfs; qa.ctr = 0;
+        LAUNCHB(KT_VALIDATE, g_validate_fast, (nfs + 63) / 64, 256, st, T, W, dSD, nfs);
+        // as many workgroups as can be resident (two per CU): the memo-miss re-validation (a quarter to a third of the frames of steady
+        // material) is spread over all of them -- a quarter-chip grid was tried and doubled this stage's time
+        int fgrid = (nfs + 63) / 64;
+        if (ctx->fixup_wg_per_cu == 0) {      // once per context: how many of this build's g_fixup workgroups a CU really holds (a grid barrier needs them all resident)
+            int nb = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)g_fixup, 64 * QWAVES, 0) != hipSuccess || nb < 1) nb = 1;
+            ctx->fixup_wg_per_cu = nb < LHIP_FIXUP_OCC / 2 ? nb : LHIP_FIXUP_OCC / 2;
+        }
+        if (fgrid > ctx->num_cus * ctx->fixup_wg_per_cu) fgrid = ctx->num_cus * ctx->fixup_wg_per_cu;
+        if (fgrid < 1) fgrid = 1;
+        if (fgrid == 1) LAUNCHB(KT_VALIDATE, g_fixup, 1, 64 * QWAVES, st, qa);
+        else {
+            kt_begin(KT_VALIDATE, st);
+            void* kargs[] = {(void*)&qa};
+            // An aliased context (tests, LHIP_ALIAS_DEVICES) runs on a stream the library created, and its batches come from worker threads: after a cooperative
+            // launch on such a stream from a thread that has since ended, ROCm 7.2's own exit handler crashes inside the HSA runtime (seen on gfx950: every variant
+            // without the cooperative launch, or on the null stream, or from the main thread, exits cleanly).  So there the launch goes through the null
+            // stream, ordered behind / in front of the context's stream by two events.
+            hipStream_t cst = (hipStream_t)st;
+            if (ctx->own_stream) {
+                if (!ctx->ev_coop[0]) { if (!rt::event_create(&ctx->ev_coop[0]) || !rt::event_create(&ctx->ev_coop[1])) return false; }
+                if (!rt::event_record(ctx->ev_coop[0], st) || !rt::stream_wait_event(nullptr, ctx->ev_coop[0])) return false;
+                cst = nullptr;
+            }
+            hipError_t e_ = hipLaunchCooperativeKernel((const void*)g_fixup, dim3(fgrid), dim3(64 * QWAVES), kargs, 0, cst);
+            if (ctx->own_stream && e_ == hipSuccess) { if (!rt::event_record(ctx->ev_coop[1], nullptr) || !rt::stream_wait_event(st, ctx->ev_coop[1])) return false; }
+            kt_end(st);
+            TRACE_SYNC(g_fixup_cooperative, st);
+            if (e_ != hipSuccess) { set_err(std::string("g_fixup (cooperative launch): ") + hipGetErrorString(e_)); return false; }
+        }
+    }
+    LAUNCH(KT_BITS, g_bits, nfs, st, T, W, dSD);
+    }
+    LAUNCH(KT_SAVE, g_save, S, st, T, W, dSD, dIO);
+    }
+    return true;
+}

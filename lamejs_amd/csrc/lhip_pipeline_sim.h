@@ -1,0 +1,152 @@
+// lhip_pipeline_sim.h -- run_pipeline of the CPU simulations (-DLHIP_HOSTSIM: one lane; with -DLHIP_WAVESIM: 64 lanes as fibers, workgroups as
+// in the kernels): the same kernel bodies in the launch order of lhip_pipeline_hip.h.  Exactly one of the two is included (lhip_batch.h).
+// Part of lhip_api.cpp's one translation unit (included there, in the order the definitions need).
+#pragma once
+// WAVE_RUN: one wave of a kernel body.  Scalar simulation: the body runs once with lane 0 (NL = 1); wave simulation
+// (-DLHIP_WAVESIM): its 64 lanes run as fibers and meet at every wave primitive (lhip_wave.h).
+#ifdef LHIP_WAVESIM
+#define WAVE_RUN(...) wsim::run([&](int lane_) { __VA_ARGS__; })
+#else
+#define WAVE_RUN(...) do { const int lane_ = 0; __VA_ARGS__; } while (0)
+#endif
+// QUANT_RUN: frame slot `b` once more through the quantization, as run_pipeline chose for the batch (`pair`)
+#ifdef LHIP_WAVESIM
+#define QUANT_RUN(chain_) do { if (pair) wsim::run_block(2, [&](int wave_, int lane_) { kb_quant<1, 0>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ2[wave_], QT, wave_, mbox); }); \
+                       else WAVE_RUN(kb_quant<0, 0>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ, QT)); } while (0)
+#else
+#define QUANT_RUN(chain_) WAVE_RUN(kb_quant<0, 0>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ, QT))
+#endif
+static inline bool g_kt_on_() { return false; }
+static bool collect_kernel_times(void*) { return true; }
+static bool collect_repair_stats(Context*, BatchPlan&, bool, const int32_t*) { return true; }      // (run_pipeline counted them itself)
+static bool run_pipeline(Context*, BatchPlan& P) {
+    const TableSet& ts = *P.ts; const Tables& T = ts.T; Workspace& W = P.W; const std::vector<StreamDesc>& sd = P.sd;
+    const StreamDesc* dSD = P.dSD; const StreamIO* dIO = P.dIO;
+    const int S = P.S, C = T.channels_out, ngs = P.ngs, nfs = P.nfs, nfr = P.nfr; const bool resv = P.resv, use_frame = P.use_frame;
+    int64_t& repaired = P.repaired; int64_t& iters = P.iters;
+    if (P.count_rej) g_rejected = (int64_t)kb_count_rejected(dIO, S, T.channels_in, T.pcm_limit, 0, 1);
+    // (thread_local: with LHIP_HOSTSIM_DEVICES > 1 host threads batch on different contexts at the same time)
+    static thread_local PsyALds LA; static thread_local PsyBLds4 LB; static thread_local MdctLds LM; static thread_local PolyLds LP; static thread_local QuantLds LQ; static thread_local BitsLds LBi; static thread_local QuantTabs QT;
+    q_load_tabs(T, QT, 0, 1);
+    if (use_frame) {
+        // the one-frame-per-stream program (kb_frame_stage), stage by stage; the wave simulation runs it as a real workgroup
+        const int NW = FR_WAVES;
+        alignas(16) static thread_local unsigned char UL[FR_WAVES][FR_LDS_PER_WAVE]; static thread_local int fmbox[12]; static thread_local CountShare fcs[2];
+        for (int s = 0; s < S; s++) {
+            fcs[0].state = CS_IDLE; fcs[1].state = CS_IDLE;      // per workgroup, as g_frame does (a stream's owners leave CS_QUIT behind)
+#ifdef LHIP_WAVESIM
+            wsim::run_block(NW, [&](int wave_, int lane_) {
+                for (int stage = 0; stage < FR_STAGES; stage++) {
+                    if (resv ? frame_stage_empty<1>(stage, T) : frame_stage_empty<0>(stage, T)) continue;
+                    if (resv) kb_frame_stage<1, 1>(stage, T, ts.pb10, W, dSD, dIO, s, wave_, NW, lane_, UL[wave_], QT, fmbox, fcs);
+                    else kb_frame_stage<0, 1>(stage, T, ts.pb10, W, dSD, dIO, s, wave_, NW, lane_, UL[wave_], QT, fmbox, fcs);
+                    wg_barrier();
+                }
+            });
+#else
+            for (int stage = 0; stage < FR_STAGES; stage++)
+                for (int wv = 0; wv < NW; wv++) {
+                    if (resv) kb_frame_stage<1, 0>(stage, T, ts.pb10, W, dSD, dIO, s, wv, NW, 0, UL[wv], QT, fmbox);
+                    else kb_frame_stage<0, 0>(stage, T, ts.pb10, W, dSD, dIO, s, wv, NW, 0, UL[wv], QT, fmbox);
+                }
+#endif
+        }
+        if (resv) for (int s = 0; s < S; s++) if (sd[s].flush) WAVE_RUN(kb_resv_flush(T, W, s, lane_, LBi, dIO[s].state->rv, W.out_bytes + s));
+    } else {
+    for (int s = 0; s < S; s++) WAVE_RUN(kb_load(T, W, dSD, dIO, s, lane_));
+    if (T.rs_ratio != 1) kb_prep(T, W, dSD, dIO, S, 0, 1);
+    for (int b = 0; b < ngs * C; b++) WAVE_RUN(kb_psyA(T, W, dSD, dIO, b / C, b % C, lane_, LA));
+    if (T.psy_channels == 4) for (int b = 0; b < ngs * 2; b++) WAVE_RUN(kb_psyA(T, W, dSD, dIO, b / 2, 2 + b % 2, lane_, LA));
+    for (int b = 0; b < ngs; b++) kb_scan_raw(T, W, dSD, b);
+    for (int b = 0; b < ngs; b++) kb_scan_attack(T, W, dSD, b);
+    for (int b = 0; b < ngs; b++) kb_scan_blocktype(T, W, dSD, b);
+#ifdef LHIP_WAVESIM
+    { static thread_local AthLds LAth; for (int s = 0; s < S; s++) wsim::run_block(ATH_NT / 64, [&](int wave_, int lane_) { kb_scan_ath(T, W, dSD, s, 64 * wave_ + lane_, LAth); }); }
+#else
+    { static thread_local AthLds LAth; for (int s = 0; s < S; s++) kb_scan_ath(T, W, dSD, s, 0, LAth); }
+#endif
+    if (!resv) for (int b = 0; b < ngs; b++) WAVE_RUN(kb_psyB<4>(T, ts.pb10, W, dSD, b, lane_, LB, -1));
+    for (int b = 0; b < (ngs * C + POLY_PER_WAVE - 1) / POLY_PER_WAVE; b++) WAVE_RUN(kb_polyphase(T, W, dSD, dIO, b, ngs * C, lane_, LP));
+    for (int b = 0; b < ngs; b++) WAVE_RUN(kb_mdct(T, W, dSD, b, lane_, LM));
+    if (resv) {
+        // the per-stream reservoir program (kb_resv_stage), as g_resv_stream runs it; the wave simulation as a real workgroup of four waves
+        alignas(16) static thread_local unsigned char RU[RS_WAVES][RS_LDS_PER_WAVE]; static thread_local int rmbox[4]; static thread_local CountShare rcs[2];
+        for (int s = 0; s < S; s++) {
+            ResvState RV = dIO[s].state->rv;
+            int32_t nout = 0;
+            const int F = sd[s].nframes;
+#ifdef LHIP_WAVESIM
+            wsim::run_block(RS_WAVES, [&](int wave_, int lane_) {
+                for (int k = 0; k <= F; k++)
+                    for (int stage = 0; stage < RS_STAGES; stage++) { kb_resv_stage<1>(stage, T, ts.pb10, W, dSD, s, k, F, wave_, lane_, RU[wave_], QT, rmbox, RV, &nout, rcs); wg_barrier(); }
+                if (wave_ == 3 && sd[s].flush) kb_resv_flush(T, W, s, lane_, *(BitsLds*)RU[3], RV, &nout);
+            });
+#else
+            for (int k = 0; k <= F; k++)
+                for (int stage = 0; stage < RS_STAGES; stage++)
+                    for (int wv = 0; wv < RS_WAVES; wv++) kb_resv_stage<0>(stage, T, ts.pb10, W, dSD, s, k, F, wv, 0, RU[wv], QT, rmbox, RV, &nout);
+            if (sd[s].flush) kb_resv_flush(T, W, s, 0, *(BitsLds*)RU[3], RV, &nout);
+#endif
+            dIO[s].state->rv = RV;
+            W.out_bytes[s] = nout;
+        }
+    } else {
+#ifdef LHIP_WAVESIM
+    // small stereo batches: the two-waves-per-frame latency kernel (kb_quant<1>), as run_batch chooses on the device
+    static thread_local QuantLds LQ2[2]; static thread_local int mbox[4];
+    static const int pair_max = []() { const char* e = getenv("LAMEJS_HIP_PAIR_MAX_FRAMES"); return e ? atoi(e) : 12; }();
+    const bool pair = (C == 2 && nfs <= pair_max);
+#endif
+#if defined(LHIP_WAVESIM)
+    if (!pair) {   // the persistent kernel as a real 8-wave workgroup: frames drawn from a shared counter (kb_quant_th, what g_quant runs for one- and
+                    // two-channel streams alike), then -- two channels -- the waves help each other (k_quant_tail.h)
+        static thread_local QuantLds LQ8[8]; static thread_local TailShare TS;
+        int ctr = 0;
+        TS.drawing = 8; for (int w = 0; w < 8; w++) TS.offer[w].state = 0;
+        wsim::run_block(8, [&](int wave_, int lane_) {
+            int hint[3] = {-1, -1, -1};
+            for (;;) {
+                int f = 0;
+                if (lane_ == 0) f = ctr++;
+                f = wave_bcast(f, 0);
+                if (f >= nfs) break;
+                kb_quant_th(T, ts.pb10, W, dSD, f, lane_, LQ8[wave_], QT, hint, TS, wave_);
+            }
+            if (C == 2) tail_help(T, ts.pb10, W, dSD, lane_, LQ8, wave_, 8, QT, TS);
+        });
+    } else
+#endif
+    {   // the speculative pass as three "persistent waves" striding over the frame slots, each with its own seed hint -- what g_quant's
+        // waves do with the frames they draw (kb_quant: `hint`), so that the simulations cover that path too
+        int hints[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};
+        for (int b = 0; b < nfs; b++) {
+#ifdef LHIP_WAVESIM
+            if (pair) { QUANT_RUN(0); continue; }
+            int hl[64][3];                                     // every lane fiber updates its own copy; they must agree (wave-uniform)
+            for (int l = 0; l < 64; l++) for (int q = 0; q < 3; q++) hl[l][q] = hints[b % 3][q];
+            WAVE_RUN(kb_quant<0, 0>(T, ts.pb10, W, dSD, b, 0, lane_, LQ, QT, -1, nullptr, nullptr, hl[lane_]));
+            for (int l = 1; l < 64; l++) for (int q = 0; q < 3; q++) if (hl[l][q] != hl[0][q]) { set_err("wavesim: seed hint not wave-uniform"); return false; }
+            for (int q = 0; q < 3; q++) hints[b % 3][q] = hl[0][q];
+#else
+            WAVE_RUN(kb_quant<0, 0>(T, ts.pb10, W, dSD, b, 0, lane_, LQ, QT, -1, nullptr, nullptr, hints[b % 3]));
+#endif
+        }
+    }
+    for (;;) {
+        W.nflagged[0] = 0; W.nflagged[1] = 0;
+        for (int b = 0; b < nfs; b++) kb_validate_fast(T, W, dSD, b);
+        for (int i = 0; i < W.nflagged[1]; i++) WAVE_RUN(kb_validate(T, ts.pb10, W, dSD, W.slow_list[i], lane_, LQ, QT));
+        const int nf = W.nflagged[0];
+        if (nf == 0) break;
+        repaired += nf; iters++;
+        for (int b = 0; b < nfs; b++) QUANT_RUN(1);
+        if (iters > nfr + 2) { set_err("seed-chain repair did not converge"); return false; }
+    }
+    for (int b = 0; b < nfs; b++) WAVE_RUN(kb_bits(T, W, dSD, b, lane_, LBi));
+    }
+    for (int s = 0; s < S; s++) WAVE_RUN(kb_save(T, W, dSD, dIO, s, lane_));
+    }
+    return true;
+}
+#undef QUANT_RUN
+#undef WAVE_RUN

@@ -458,7 +458,7 @@ LHIP_DEV void wg_meet(int* p, int n, int lane) {
 #endif
 }
 // A poll loop that has gone round this often (seconds; a launch's tail is milliseconds) is a protocol or compiler bug: fault instead of
-// hanging the device (lhip_api.cpp, g_fixup: a dispenser loop nested in another loop has been miscompiled into an exec-masked loop on this
+// hanging the device (lhip_kernels.h, g_fixup: a dispenser loop nested in another loop has been miscompiled into an exec-masked loop on this
 // toolchain before).
 #if defined(LHIP_HOSTSIM)
 #define LHIP_SPIN_GUARD(n) do { if (++(n) > (1l << 34)) abort(); } while (0)

@@ -712,7 +712,7 @@ def test_gpu_two_devices_round_robin_and_concurrent_batches(lib):
     from oracle_py import oracle_encode
     import os
     aliased = lib.lhip_device_count() < 2
-    if aliased:         # one GPU: ordinals 0 and 1 become two SEPARATE library contexts (mutex, HIP stream, workspaces, table uploads) on it (lhip_api.cpp rt::alias_n)
+    if aliased:         # one GPU: ordinals 0 and 1 become two SEPARATE library contexts (mutex, HIP stream, workspaces, table uploads) on it (lhip_rt.h rt::alias_n)
         os.environ["LHIP_ALIAS_DEVICES"] = "2"
         assert lib.lhip_device_count() == 2
     lib.lhip_set_devices.restype = ctypes.c_int
@@ -810,7 +810,7 @@ def _segmented_material(seed, nfr, seg_frames=3000):
 
 def test_gpu_host_call_in_overlapped_chunks(lib, tmp_path):
     """ONE lhip_encode call with HOST buffers, cut by the library into chunks whose copies overlap the encode of the chunk before
-    (lhip_api.cpp encode_host_chunked; two-channel schedule: 16384 frames, doubling, capped at 65536, a short remainder merged into the
+    (lhip_hostcall.h encode_host_chunked; two-channel schedule: 16384 frames, doubling, capped at 65536, a short remainder merged into the
     chunk before it when that still fits the cap), on RANDOM two-channel material -- the case the steady bench stream never exercises:
     speculation-seed misses and repairs inside a chunk, the carry across chunk edges, flush() after a chunked call.
       * stereo, 120 000 frames: chunks of 16384 + 32768 + 65536 (the cap) + a short last one
