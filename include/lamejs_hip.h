@@ -213,6 +213,30 @@ int lhip_set_hip_stream(int device, void* hip_stream);
  * the bin-search seed repair pass, repair iterations. */
 void lhip_last_batch_stats(int64_t* frames, int64_t* repaired_frames, int64_t* repair_iterations);
 
+/* Debug/test hook: which launch paths the most recent batch on the calling thread took -- a host-side record of the decisions the library
+ * made from the batch's shape and the device's CU count (no kernel is changed or synchronised for it); a long host call that was cut into
+ * units reports every path one of its units took.  One bit per decision:
+ *   LHIP_PATH_FRAME 0x1 (the one-launch frame program, g_frame<0>), FRAME_RESV 0x2 (g_frame<1>, bit reservoir), SEPARATE 0x4 (the separate
+ *   kernels), PREP 0x8 (the resampler materialises samples), PSY4 0x10 (joint stereo's second analysis launch), QUANT_PAIR 0x20 (g_quant_pair),
+ *   QUANT_PERSISTENT 0x40 (g_quant, for two channels with the tail help), RESV_STREAM_HELPERS 0x80 / RESV_STREAM_NOHELPERS 0x100 (g_resv_stream
+ *   with / without its count helpers), RESV_FLUSH 0x200 (g_resv_flush behind the frame program), FIXUP_SINGLE 0x400 / FIXUP_COOP 0x800 (g_fixup as
+ *   one workgroup / as a cooperative launch), SMALL_CALL 0x1000 (everything in one pinned block).
+ * Returns 0, or < 0 for a null pointer. */
+#define LHIP_PATH_FRAME 0x1u
+#define LHIP_PATH_FRAME_RESV 0x2u
+#define LHIP_PATH_SEPARATE 0x4u
+#define LHIP_PATH_PREP 0x8u
+#define LHIP_PATH_PSY4 0x10u
+#define LHIP_PATH_QUANT_PAIR 0x20u
+#define LHIP_PATH_QUANT_PERSISTENT 0x40u
+#define LHIP_PATH_RESV_STREAM_HELPERS 0x80u
+#define LHIP_PATH_RESV_STREAM_NOHELPERS 0x100u
+#define LHIP_PATH_RESV_FLUSH 0x200u
+#define LHIP_PATH_FIXUP_SINGLE 0x400u
+#define LHIP_PATH_FIXUP_COOP 0x800u
+#define LHIP_PATH_SMALL_CALL 0x1000u
+int lhip_debug_last_paths(uint32_t* mask);
+
 /* Debug/test taps (tests only): copy intermediate results of the most recent batch to the host.
  * what: 0 xr [granule][ch][576] f32, 1 blocktype [granule][ch] i32, 2 E [granule][psy ch][122] f32 (psy ch = ch, or L R mid side in joint stereo; thresholds
  * handed to the quantizer for that granule), 3 ath_adjust [frame] f64, 4 side records (struct GrSide).

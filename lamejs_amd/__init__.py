@@ -22,7 +22,24 @@ _PKG = Path(__file__).resolve().parent
 _LIB_PATH = _PKG / "lib" / "liblamejs_hip.so"
 _TABLE_DIR = _PKG / "tables"
 
-__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED"]
+__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED", "PATH_NAMES", "last_batch_paths"]
+
+# launch paths of a batch (include/lamejs_hip.h: LHIP_PATH_*), in bit order
+PATH_NAMES = ("FRAME", "FRAME_RESV", "SEPARATE", "PREP", "PSY4", "QUANT_PAIR", "QUANT_PERSISTENT", "RESV_STREAM_HELPERS", "RESV_STREAM_NOHELPERS",
+              "RESV_FLUSH", "FIXUP_SINGLE", "FIXUP_COOP", "SMALL_CALL")
+
+
+def last_batch_paths(lib=None) -> frozenset:
+    """Names of the launch paths the most recent batch on this thread took (``lhip_debug_last_paths``; a debug/test hook)."""
+    lib = lib or load_library()
+    m = ctypes.c_uint32()
+    rc = lib.lhip_debug_last_paths(ctypes.byref(m))
+    if rc != 0:
+        raise LhipError(f"lhip_debug_last_paths failed ({rc}): {lib.lhip_last_error().decode()}")
+    if m.value >> len(PATH_NAMES):
+        raise LhipError(f"lhip_debug_last_paths: unknown bits in {m.value:#x}")
+    return frozenset(n for i, n in enumerate(PATH_NAMES) if m.value >> i & 1)
+
 
 # sample formats of the *_pcm entries (include/lamejs_hip.h: LHIP_PCM_*): a sample type, optionally or-ed with PCM_INTERLEAVED
 PCM_S16, PCM_F32, PCM_INTERLEAVED = 0, 1, 2
@@ -80,6 +97,8 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
     lib.lhip_set_hip_stream.argtypes = [ctypes.c_int, ctypes.c_void_p]
     lib.lhip_last_batch_stats.restype = None
     lib.lhip_last_batch_stats.argtypes = [ctypes.POINTER(ctypes.c_int64)] * 3
+    lib.lhip_debug_last_paths.restype = ctypes.c_int
+    lib.lhip_debug_last_paths.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
     lib.lhip_debug_read.restype = ctypes.c_int64
     lib.lhip_debug_read.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
     lib.lhip_last_error.restype = ctypes.c_char_p
@@ -322,6 +341,10 @@ class Mp3Encoder:
         a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         self._lib.lhip_last_batch_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
         return {"frames": a.value, "repaired_frames": b.value, "repair_iterations": c.value}
+
+    def last_batch_paths(self) -> frozenset:
+        """Which launch paths the most recent batch on this thread took, as a set of names (``PATH_NAMES``; include/lamejs_hip.h)."""
+        return last_batch_paths(self._lib)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -585,6 +585,12 @@ void lhip_last_batch_stats(int64_t* frames, int64_t* repaired_frames, int64_t* r
     if (repair_iterations) *repair_iterations = g_stat_iters;
 }
 
+int lhip_debug_last_paths(uint32_t* mask) {
+    if (!mask) { set_err("lhip_debug_last_paths: null argument"); return LHIP_ERR_INTERNAL; }
+    *mask = g_last_paths;
+    return 0;
+}
+
 int64_t lhip_debug_read(int what, void* dst, size_t cap) {
 #ifdef LHIP_PHASE_PROF
     if (what == 9) { const size_t n = cap < sizeof g_call_prof ? cap : sizeof g_call_prof; memcpy(dst, g_call_prof, n); return (int64_t)n; }

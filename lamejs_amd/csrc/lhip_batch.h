@@ -114,6 +114,7 @@ struct BatchPlan {
     TableSet* ts = nullptr;
     bool dev_io = false, resv = false, count_rej = false, use_frame = false, small = false;
     int S = 0, nfs = 0, ngs = 0, nfr = 0, maxF = 0;
+    uint32_t paths = 0;                            // LHIP_PATH_*: one bit per launch decision run_pipeline really takes for this batch (host-side record only)
     int64_t pcm_plane = 0, in_total = 0, out_total = 0, repaired = 0, iters = 0;
     size_t in_bytes = 0, FR = 1;                   // in_bytes: host input as it travels: every job's samples in its format, jobs 4-byte aligned
     std::vector<StreamDesc> sd; std::vector<StreamIO> io;
@@ -202,6 +203,7 @@ static bool bind_workspace(Context* ctx, BatchPlan& P) {
         W.nflagged = (int32_t*)(smb + L.sm_nfl); W.work_ctr = W.nflagged + 16; W.out_bytes = (int32_t*)(smb + L.sm_ob);
         W.seed_flag = (int32_t*)(smb + L.sm_sf); W.reval = (int32_t*)(smb + L.sm_rv);
     } else if (!P.dev_io && !(ws.in16.ensure(P.in_bytes + 64) && ws.out8.ensure((size_t)P.out_total + 64))) return false;
+    if (P.small) P.paths |= LHIP_PATH_SMALL_CALL;
     return true;
 }
 static bool stage_inputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P) {
@@ -378,7 +380,7 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     CALL_STAMP(3);                                  // output copies + synchronisation
     advance_streams(jobs, P.ts->T);
     if (!collect_repair_stats(ctx, P, fetch_fx, fx)) return false;
-    g_stat_frames = P.nfr; g_stat_repaired = P.repaired; g_stat_iters = P.iters;
+    g_stat_frames = P.nfr; g_stat_repaired = P.repaired; g_stat_iters = P.iters; g_last_paths = P.paths;
     WorkSet& ws = ctx->ws;
     ws.lastW = P.W; ws.lastC = P.ts->T.channels_out; ws.lastCp = P.ts->T.psy_channels; ws.have_last = true;
     return true;

@@ -80,6 +80,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
     }
     void* cs = ctx->copy_stream; void* ks = ctx->stream;
     int64_t frames_all = 0, repaired_all = 0, iters_all = 0;
+    uint32_t paths_all = 0;
     std::vector<int64_t> total(NS, 0);
     struct Pending { uint8_t* dst; const uint8_t* src; int64_t bytes; };
     std::vector<Pending> pending; int pending_par = 0; bool have_pending = false;      // the unit whose output is still on the device
@@ -153,7 +154,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
             total[si] += jobs[j].written;
         }
         pending_par = par; have_pending = true;
-        frames_all += g_stat_frames;
+        frames_all += g_stat_frames; paths_all |= g_last_paths;
     }
     if (!drain()) return fail(nullptr);
     if (trace_chunks) fprintf(stderr, "[lhip units] last unit's bytes home %.2f ms\n", ms_now());
@@ -168,6 +169,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
     g_stat_pending = nullptr;
 #endif
     g_stat_frames = frames_all; g_stat_repaired = repaired_all; g_stat_iters = iters_all;     // lhip_last_batch_stats: the whole call
+    g_last_paths = paths_all;                                                                 // lhip_debug_last_paths: every path one of its units took
     for (size_t i = 0; i < NS; i++) written[i] = total[i];
     return 0;
 }

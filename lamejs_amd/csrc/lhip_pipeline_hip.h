@@ -29,9 +29,11 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     }
     if (use_frame) {
         QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;
+        P.paths |= resv ? LHIP_PATH_FRAME_RESV : LHIP_PATH_FRAME;
         if (resv) LAUNCHB(KT_QUANT, g_frame<1>, S, 64 * FR_WAVES, st, qa, dIO); else LAUNCHB(KT_QUANT, g_frame<0>, S, 64 * FR_WAVES, st, qa, dIO);
-        if (resv) { bool any_flush = false; for (int i = 0; i < S; i++) any_flush |= sd[i].flush != 0; if (any_flush) LAUNCH(KT_BITS, g_resv_flush, S, st, T, W, dSD); }
+        if (resv) { bool any_flush = false; for (int i = 0; i < S; i++) any_flush |= sd[i].flush != 0; if (any_flush) { P.paths |= LHIP_PATH_RESV_FLUSH; LAUNCH(KT_BITS, g_resv_flush, S, st, T, W, dSD); } }
     } else {
+    P.paths |= LHIP_PATH_SEPARATE | (T.rs_ratio != 1 ? LHIP_PATH_PREP : 0) | (T.psy_channels == 4 ? LHIP_PATH_PSY4 : 0);
     LAUNCH(KT_LOAD, g_load, S, st, T, W, dSD, dIO);
     if (T.rs_ratio != 1) {          // only the resampler materialises samples; otherwise the consumers convert the caller's Int16 themselves
         int64_t nb = (in_total / C + 255) / 256;
@@ -76,6 +78,7 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
         //  per CU a helper shares its SIMD with the other workgroup's searching wave and the speculative work costs more than it hides --
         //  512 streams: 2.37 M frames/s without helpers, 2.21 M with, profiles/r05_pass4_* / r05_pass5_*)
         QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 2; qa.nfs = nfs; qa.ctr = S <= ctx->num_cus ? 1 : 0;
+        P.paths |= qa.ctr ? LHIP_PATH_RESV_STREAM_HELPERS : LHIP_PATH_RESV_STREAM_NOHELPERS;
         LAUNCHB(KT_QUANT, g_resv_stream, S, 64 * RS_WAVES, st, qa);
     } else {
     if (T.psy_channels == 4) LAUNCHB(KT_PSYB, g_psyB<4>, XCD_GRID_W(ngs), 64 * WPB, st, T, ts.pb10, W, dSD, -1);
@@ -92,6 +95,7 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     static const int pair_max = []() { const char* e = getenv("LAMEJS_HIP_PAIR_MAX_FRAMES"); return e ? atoi(e) : -1; }();
     const bool pair = (C == 2 && nfs <= (pair_max >= 0 ? pair_max : 6 * ctx->num_cus));
 #endif
+    P.paths |= pair ? LHIP_PATH_QUANT_PAIR : LHIP_PATH_QUANT_PERSISTENT;
     { QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;
       if (pair) LAUNCHB(KT_QUANT, g_quant_pair<0>, nfs, 128, st, qa); else LAUNCHB(KT_QUANT, g_quant<0>, qgrid, 64 * QWAVES, st, qa); }
     if (nfr > 0) {
@@ -108,6 +112,7 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
         }
         if (fgrid > ctx->num_cus * ctx->fixup_wg_per_cu) fgrid = ctx->num_cus * ctx->fixup_wg_per_cu;
         if (fgrid < 1) fgrid = 1;
+        P.paths |= fgrid == 1 ? LHIP_PATH_FIXUP_SINGLE : LHIP_PATH_FIXUP_COOP;
         if (fgrid == 1) LAUNCHB(KT_VALIDATE, g_fixup, 1, 64 * QWAVES, st, qa);
         else {
             kt_begin(KT_VALIDATE, st);

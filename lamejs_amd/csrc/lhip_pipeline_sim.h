@@ -19,6 +19,8 @@
 static inline bool g_kt_on_() { return false; }
 static bool collect_kernel_times(void*) { return true; }
 static bool collect_repair_stats(Context*, BatchPlan&, bool, const int32_t*) { return true; }      // (run_pipeline counted them itself)
+// P.paths: the simulations record what they simulate -- the scalar one has no two-waves-per-frame program and no count helpers, the wave
+// simulation always runs the count helpers, and neither has g_fixup's two launch forms (the repair is the host loop below): no FIXUP bit
 static bool run_pipeline(Context*, BatchPlan& P) {
     const TableSet& ts = *P.ts; const Tables& T = ts.T; Workspace& W = P.W; const std::vector<StreamDesc>& sd = P.sd;
     const StreamDesc* dSD = P.dSD; const StreamIO* dIO = P.dIO;
@@ -29,6 +31,7 @@ static bool run_pipeline(Context*, BatchPlan& P) {
     static thread_local PsyALds LA; static thread_local PsyBLds4 LB; static thread_local MdctLds LM; static thread_local PolyLds LP; static thread_local QuantLds LQ; static thread_local BitsLds LBi; static thread_local QuantTabs QT;
     q_load_tabs(T, QT, 0, 1);
     if (use_frame) {
+        P.paths |= resv ? LHIP_PATH_FRAME_RESV : LHIP_PATH_FRAME;
         // the one-frame-per-stream program (kb_frame_stage), stage by stage; the wave simulation runs it as a real workgroup
         const int NW = FR_WAVES;
         alignas(16) static thread_local unsigned char UL[FR_WAVES][FR_LDS_PER_WAVE]; static thread_local int fmbox[12]; static thread_local CountShare fcs[2];
@@ -51,8 +54,10 @@ static bool run_pipeline(Context*, BatchPlan& P) {
                 }
 #endif
         }
+        if (resv) for (int s = 0; s < S; s++) if (sd[s].flush) P.paths |= LHIP_PATH_RESV_FLUSH;
         if (resv) for (int s = 0; s < S; s++) if (sd[s].flush) WAVE_RUN(kb_resv_flush(T, W, s, lane_, LBi, dIO[s].state->rv, W.out_bytes + s));
     } else {
+    P.paths |= LHIP_PATH_SEPARATE | (T.rs_ratio != 1 ? LHIP_PATH_PREP : 0) | (T.psy_channels == 4 ? LHIP_PATH_PSY4 : 0);
     for (int s = 0; s < S; s++) WAVE_RUN(kb_load(T, W, dSD, dIO, s, lane_));
     if (T.rs_ratio != 1) kb_prep(T, W, dSD, dIO, S, 0, 1);
     for (int b = 0; b < ngs * C; b++) WAVE_RUN(kb_psyA(T, W, dSD, dIO, b / C, b % C, lane_, LA));
@@ -70,6 +75,11 @@ static bool run_pipeline(Context*, BatchPlan& P) {
     for (int b = 0; b < ngs; b++) WAVE_RUN(kb_mdct(T, W, dSD, b, lane_, LM));
     if (resv) {
         // the per-stream reservoir program (kb_resv_stage), as g_resv_stream runs it; the wave simulation as a real workgroup of four waves
+#ifdef LHIP_WAVESIM
+        P.paths |= LHIP_PATH_RESV_STREAM_HELPERS;
+#else
+        P.paths |= LHIP_PATH_RESV_STREAM_NOHELPERS;
+#endif
         alignas(16) static thread_local unsigned char RU[RS_WAVES][RS_LDS_PER_WAVE]; static thread_local int rmbox[4]; static thread_local CountShare rcs[2];
         for (int s = 0; s < S; s++) {
             ResvState RV = dIO[s].state->rv;
@@ -96,6 +106,9 @@ static bool run_pipeline(Context*, BatchPlan& P) {
     static thread_local QuantLds LQ2[2]; static thread_local int mbox[4];
     static const int pair_max = []() { const char* e = getenv("LAMEJS_HIP_PAIR_MAX_FRAMES"); return e ? atoi(e) : 12; }();
     const bool pair = (C == 2 && nfs <= pair_max);
+    P.paths |= pair ? LHIP_PATH_QUANT_PAIR : LHIP_PATH_QUANT_PERSISTENT;
+#else
+    P.paths |= LHIP_PATH_QUANT_PERSISTENT;
 #endif
 #if defined(LHIP_WAVESIM)
     if (!pair) {   // the persistent kernel as a real 8-wave workgroup: frames drawn from a shared counter (kb_quant_th, what g_quant runs for one- and

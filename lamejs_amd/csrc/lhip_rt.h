@@ -17,6 +17,7 @@ enum { PROF_BYTES = 512 };
 struct Context;
 static thread_local Context* g_rej_pending = nullptr;       // the last batch counted rejected Float32 samples on the device (lhip_last_batch_rejected_samples fetches the count)
 static thread_local int64_t g_rejected = 0;
+static thread_local uint32_t g_last_paths = 0;              // launch decisions of the last batch (LHIP_PATH_* of include/lamejs_hip.h; lhip_debug_last_paths)
 static thread_local Context* g_stat_pending = nullptr;      // the last batch was enqueued without synchronisation: its repair statistics are still on the device
 static void set_err(const std::string& e) { g_err = e; }
 

@@ -99,7 +99,7 @@ static int lo_load_cfg(lo_cfg* c, const void* blob_in, size_t nbytes) {
     c->version_bytes = (const int32_t*)lo_arr(b, "version_bytes", 1, &c->n_version_bytes);
     AD(fht_twiddle); AD(fht_costab); AD(enwindow); AD(mdct_win); AD(ma_tab); AD(ma_table1); AD(ma_table2);
     AD(ma_table3); AD(hpf_fircoef);
-    if (c->quant_comp != 9 || c->quant_comp_short != 9 || (c->version != 1 && c->version != 0) || c->mode_gr != (c->version == 1 ? 2 : 1) || c->error_protection) {
+    if (c->quant_comp != 9 || c->quant_comp_short != 9 || (c->version != 1 && c->version != 0) || c->mode_gr != (c->version == 1 ? 2 : 1)) {
         fprintf(stderr, "lame_oracle: configuration outside the supported envelope\n");
         return -1;
     }
@@ -201,6 +201,7 @@ static int lo_format_frame(lo_enc* e, uint8_t* out, int* main_bits) {
     lo_put(&w, (uint32_t)c->copyright, 1);
     lo_put(&w, (uint32_t)c->original, 1);
     lo_put(&w, (uint32_t)c->emphasis, 2);
+    if (c->error_protection) lo_put(&w, 0, 16);         /* the CRC's place (BitStream.js:283-285), filled in below */
     if (c->version == 1) {
     /* side info (MPEG-1) */
         lo_put(&w, mdb, 9);                                 /* main_data_begin */
@@ -350,6 +351,20 @@ static int lo_format_frame(lo_enc* e, uint8_t* out, int* main_bits) {
             if (getenv("LO_DEBUG") && w.bitpos - dbg_p0 != gi->part2_3_length + gi->part2_length)
                 fprintf(stderr, "frame %ld ch %d: wrote %d, part2 %d part2_3 %d bt %d slen %d %d %d %d tab %d row %d sfc %d\n", e->frame_num, ch, w.bitpos - dbg_p0, gi->part2_length, gi->part2_3_length, gi->block_type, gi->slen[0], gi->slen[1], gi->slen[2], gi->slen[3], gi->sfb_part_tab, gi->sfb_part_row, gi->scalefac_compress);
         }
+    }
+    if (c->error_protection) {
+        /* CRC-16 of ISO 11172-3 2.4.3.1 (x^16 + x^15 + x^2 + 1, preset to ones, MSB first) over header bytes 2, 3 and the side information */
+        uint32_t crc = 0xffff;
+        int i, k;
+        for (i = 2; i < c->sideinfo_len; i++) {
+            if (i == 4 || i == 5) continue;
+            for (k = 7; k >= 0; k--) {
+                const uint32_t top = ((crc >> 15) ^ ((uint32_t)out[i] >> k)) & 1u;
+                crc = (crc << 1) & 0xffff;
+                if (top) crc ^= 0x8005;
+            }
+        }
+        out[4] = (uint8_t)(crc >> 8); out[5] = (uint8_t)(crc & 0xff);
     }
     if (main_bits) { *main_bits = w.bitpos - 8 * c->sideinfo_len; return 0; }
     lo_drain(c, &w, e->resvDrain_post);

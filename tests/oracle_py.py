@@ -11,11 +11,30 @@ _SO = ROOT / "oracle" / "_ref" / "liblame_oracle.so"
 _lib = None
 
 
+def _sources_hash() -> str:
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted((ROOT / "oracle").glob("*.[ch]")) + [ROOT / "oracle" / "Makefile"]:
+        h.update(f.name.encode() + b"\0" + f.read_bytes())
+    return h.hexdigest()
+
+
+def _make_current():
+    """The library in oracle/_ref/ is the build of the sources that are here now -- decided by CONTENT (a hash of oracle/*.c, *.h and the
+    Makefile kept beside the build), not by file times: oracle/_ref/ is untracked and can outlive the sources it was built from, with any
+    time stamp.  A build of other sources is made again from scratch; otherwise `make` only confirms it."""
+    stamp = _SO.parent / "sources.sha256"
+    want = _sources_hash()
+    fresh = _SO.exists() and stamp.exists() and stamp.read_text().strip() == want
+    subprocess.run(["make", "-C", str(ROOT / "oracle")] + ([] if fresh else ["-B"]) + ["all"], check=True, capture_output=True)
+    if not fresh:
+        stamp.write_text(want + "\n")
+
+
 def _load():
     global _lib
     if _lib is None:
-        if not _SO.exists():
-            subprocess.run(["make", "-C", str(ROOT / "oracle"), "all"], check=True, capture_output=True)
+        _make_current()          # before the first load: the process keeps the handle it loads
         lib = ctypes.CDLL(str(_SO))
         lib.lo_create.restype = ctypes.c_void_p
         lib.lo_create.argtypes = [ctypes.c_void_p, ctypes.c_size_t]

@@ -291,7 +291,8 @@ def device_sanitise_check(lib, call=gpu_device_call, long_call=9 * 1152):
 
 def device_batch_check(lib, fmt):
     """lhip_encode_batch_device_pcm with sync = 0 over torch tensors (float32 / int16, planar / interleaved): many streams of many frames
-    (g_quant), one frame per stream (g_frame), reservoir streams (g_resv_stream) == the oracle."""
+    (two channels: about 100 frame slots, which is the pair kernel g_quant_pair; one channel: g_quant), one frame per stream (g_frame), reservoir
+    streams (g_resv_stream) == the oracle."""
     from oracle_py import oracle_encode
     batches = 0
     for cfg, resv, lens in (((2, 44100, 128), False, [1152 * 40 + 7, 1152 * 25, 777, 1152 * 33 + 1]), ((2, 44100, 128), False, [1152] * 6), ((1, 44100, 128), False, [1152 * 30, 1152 * 11 + 5]),

@@ -18,6 +18,19 @@ def test_hip_library_exports_declared_symbols():
     assert b"HIP gfx950" in lib.lhip_version()
 
 
+def test_debug_last_paths_is_exported_and_mirrored():
+    """lhip_debug_last_paths: declared, exported, refuses a null pointer, reports no path before any batch; the mirror's names are the
+    header's LHIP_PATH_* bits in order."""
+    import lamejs_amd
+    lib = lamejs_amd.load_library()
+    hdr = (ROOT / "include" / "lamejs_hip.h").read_text()
+    assert re.search(r"\bint\s+lhip_debug_last_paths\s*\(\s*uint32_t\s*\*", hdr) and hasattr(lib, "lhip_debug_last_paths")
+    bits = re.findall(r"#define LHIP_PATH_([A-Z0-9_]+) (0x[0-9a-f]+)u", hdr)
+    assert [n for n, _ in bits] == list(lamejs_amd.PATH_NAMES) and [int(v, 16) for _, v in bits] == [1 << i for i in range(len(bits))] and len(bits) == 13
+    assert lib.lhip_debug_last_paths(None) < 0 and b"lhip_debug_last_paths" in lib.lhip_last_error()
+    assert lamejs_amd.last_batch_paths(lib) == frozenset()
+
+
 def test_no_cpu_fallback_without_device():
     """On a box without a HIP device creation must fail loudly (never silently fall back)."""
     import lamejs_amd

@@ -34,7 +34,9 @@ def test_gpu_every_golden_case(lib):
 @pytest.mark.parametrize("fmt", ["f32_planar", "f32_interleaved", "s16_interleaved", "mixed"])
 def test_gpu_random_family_equals_the_oracle(lib, fmt):
     """Per-stream calls: 1152-sample calls are one-frame launches (g_frame<0>, with the reservoir g_frame<1>), a few frames of two channels in
-    one call the pair kernel (g_quant_pair), long calls the persistent kernel (g_quant), several reservoir frames in one call g_resv_stream."""
+    one call the pair kernel (g_quant_pair) -- the family's calls stay at or below 60 frames, far below the pair threshold of 6 x CUs frame slots, so
+    its two-channel cases never reach the persistent kernel; its one-channel cases always take it (g_quant) --, several reservoir frames in one call
+    g_resv_stream.  (The two-channel persistent kernel on every configuration family: tests/test_path_matrix_gpu.py.)"""
     order = [S16, F32 | INTER, F32, S16 | INTER]
     fam = pc.family(20271, 84) + pc.family(20272, 28, max_frames=60)
     for i, fc in enumerate(fam):
@@ -46,7 +48,8 @@ def test_gpu_random_family_equals_the_oracle(lib, fmt):
 @pytest.mark.parametrize("fmt", sorted(pc.FORMATS))
 def test_gpu_device_resident_batch(fmt):
     """lhip_encode_batch_device_pcm with sync = 0 over torch tensors (float32 / int16, planar / interleaved): many streams of many frames
-    (g_quant), one frame per stream (g_frame), reservoir streams (g_resv_stream) == the oracle (pcmformats_cases.device_batch_check, in a
+    (two channels: about 100 frame slots, g_quant_pair; one channel: g_quant), one frame per stream (g_frame), reservoir streams (g_resv_stream)
+    == the oracle (pcmformats_cases.device_batch_check, in a
     process of its own: torch initialises the GPU before the library is loaded)."""
     r = subprocess.run([sys.executable, str(ROOT / "tests" / "pcmformats_cases.py"), "--device-batch", fmt], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])

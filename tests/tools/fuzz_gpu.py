@@ -2,7 +2,9 @@
 
 Corpora mix tones, coloured noise, silence gaps, clicks and level ramps so that short blocks, ESC Huffman tables,
 scalefac_scale / subblock_gain escalation, analog silence and the ATH recurrence all get exercised at every
-supported sample rate and a spread of bitrates.  usage: python tests/tools/fuzz_gpu.py [ncases] [seed]"""
+supported sample rate and a spread of bitrates.  That the material really contains these is asserted where it is relied on: the census of the
+oracle's side information in tests/test_path_matrix_cpu.py::test_material_is_not_trivial (tests/sideinfo.py, path_matrix_cases.census_ok).
+usage: python tests/tools/fuzz_gpu.py [ncases] [seed]"""
 import sys, time
 from pathlib import Path
 import numpy as np
