@@ -54,6 +54,51 @@ class _Config(ctypes.Structure):
                 ("device", ctypes.c_int32)]
 
 
+# The C ABI of include/lamejs_hip.h, entry -> (restype, argtypes): the one place that states it.  load_library() applies it to every library it
+# loads, so no caller declares a signature (an undeclared entry would pass Python integers as 32-bit C int: a truncation for size_t, int64_t
+# and pointers).  tests/test_abi.py holds it against the header's prototypes.
+_int, _i64, _size, _ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_void_p
+_pi32, _pi64 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+ABI = {
+    "lhip_device_count": (_int, []),
+    "lhip_set_devices": (_int, [ctypes.c_uint64]),
+    "lhip_stream_device": (_int, [_ptr]),
+    "lhip_device_identity": (_int, [_int, ctypes.c_char_p, ctypes.c_char_p, _size]),
+    "lhip_state_bytes": (_size, [_ptr]),
+    "lhip_state_get": (_int, [_ptr, _ptr, _size]),
+    "lhip_state_set": (_int, [_ptr, _ptr, _size]),
+    "lhip_seek_tail_samples": (_size, [_ptr]),
+    "lhip_seek": (_int, [_ptr, _i64, _ptr, _ptr]),
+    "lhip_create": (_int, [ctypes.POINTER(_Config), _ptr, _size, ctypes.POINTER(_ptr)]),
+    "lhip_encode": (_i64, [_ptr, _ptr, _ptr, _size, _ptr, _size]),
+    "lhip_encode_pcm": (_i64, [_ptr, _int, _ptr, _ptr, _size, _ptr, _size]),
+    "lhip_flush": (_i64, [_ptr, _ptr, _size]),
+    "lhip_destroy": (None, [_ptr]),
+    "lhip_max_output_bytes": (_size, [_ptr, _size]),
+    "lhip_encode_output_bytes": (_i64, [_ptr, _size]),
+    "lhip_output_bytes_is_exact": (_int, [_ptr]),
+    "lhip_encode_batch": (_int, [_ptr, _size] + [_ptr] * 6),
+    "lhip_encode_batch_pcm": (_int, [_ptr, _size, _int] + [_ptr] * 6),
+    "lhip_flush_batch": (_int, [_ptr, _size] + [_ptr] * 3),
+    "lhip_encode_batch_device": (_int, [_ptr, _size] + [_ptr] * 6 + [_int]),
+    "lhip_encode_batch_device_pcm": (_int, [_ptr, _size, _int] + [_ptr] * 6 + [_int]),
+    "lhip_last_batch_rejected_samples": (_i64, []),
+    "lhip_set_hip_stream": (_int, [_int, _ptr]),
+    "lhip_last_batch_stats": (None, [_pi64] * 3),
+    "lhip_debug_last_paths": (_int, [ctypes.POINTER(ctypes.c_uint32)]),
+    "lhip_debug_read": (_i64, [_int, _ptr, _size]),
+    "lhip_kernel_timing": (_int, [_int]),
+    "lhip_kernel_times": (_int, [_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double), _pi64]),
+    "lhip_debug_math": (_int, [_int, _ptr, _ptr, _size]),
+    "lhip_debug_set_spec_seed": (_int, [_int, _int]),
+    "lhip_debug_release_context": (_int, [_int]),
+    "lhip_frac_call_limit": (_i64, [_ptr]),
+    "lhip_debug_frac_call": (_int, [_ptr, _size, _pi32, _pi32]),
+    "lhip_debug_frac_flush": (_int, [_ptr, _pi32, _pi32, _int]),
+    "lhip_last_error": (ctypes.c_char_p, []),
+    "lhip_version": (ctypes.c_char_p, []),
+}
+
 _lib = None
 
 
@@ -67,42 +112,9 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         raise LhipError(f"{p} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
                         "lamejs_amd has no CPU fallback.")
     lib = ctypes.CDLL(str(p))
-    lib.lhip_device_count.restype = ctypes.c_int
-    lib.lhip_create.restype = ctypes.c_int
-    lib.lhip_create.argtypes = [ctypes.POINTER(_Config), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
-    lib.lhip_encode.restype = ctypes.c_int64
-    lib.lhip_encode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
-    lib.lhip_flush.restype = ctypes.c_int64
-    lib.lhip_flush.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-    lib.lhip_destroy.restype = None
-    lib.lhip_destroy.argtypes = [ctypes.c_void_p]
-    lib.lhip_max_output_bytes.restype = ctypes.c_size_t
-    lib.lhip_max_output_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    lib.lhip_encode_output_bytes.restype = ctypes.c_int64
-    lib.lhip_encode_output_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    lib.lhip_output_bytes_is_exact.restype = ctypes.c_int
-    lib.lhip_output_bytes_is_exact.argtypes = [ctypes.c_void_p]
-    for name in ("lhip_encode_batch", "lhip_flush_batch", "lhip_encode_batch_device"):
-        getattr(lib, name).restype = ctypes.c_int
-    # sample formats: a library without these entries is not this package's library (no fallback to the Int16 entries)
-    lib.lhip_encode_pcm.restype = ctypes.c_int64
-    lib.lhip_encode_pcm.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
-    lib.lhip_encode_batch_pcm.restype = ctypes.c_int
-    lib.lhip_encode_batch_pcm.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int] + [ctypes.c_void_p] * 6
-    lib.lhip_encode_batch_device_pcm.restype = ctypes.c_int
-    lib.lhip_encode_batch_device_pcm.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int]
-    lib.lhip_last_batch_rejected_samples.restype = ctypes.c_int64
-    lib.lhip_last_batch_rejected_samples.argtypes = []
-    lib.lhip_set_hip_stream.restype = ctypes.c_int
-    lib.lhip_set_hip_stream.argtypes = [ctypes.c_int, ctypes.c_void_p]
-    lib.lhip_last_batch_stats.restype = None
-    lib.lhip_last_batch_stats.argtypes = [ctypes.POINTER(ctypes.c_int64)] * 3
-    lib.lhip_debug_last_paths.restype = ctypes.c_int
-    lib.lhip_debug_last_paths.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
-    lib.lhip_debug_read.restype = ctypes.c_int64
-    lib.lhip_debug_read.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
-    lib.lhip_last_error.restype = ctypes.c_char_p
-    lib.lhip_version.restype = ctypes.c_char_p
+    for name, (restype, argtypes) in ABI.items():      # a library without one of these entries is not this package's library
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if path is None:
         _lib = lib
     return lib
@@ -247,14 +259,10 @@ class Mp3Encoder:
 
     def call_limit(self) -> int:
         """``fractional_resample`` streams: the ``encodeBuffer`` length that is accepted whatever calls came before (0: any length goes)."""
-        self._lib.lhip_frac_call_limit.restype = ctypes.c_int64
-        self._lib.lhip_frac_call_limit.argtypes = [ctypes.c_void_p]
         return int(self._lib.lhip_frac_call_limit(self._h))
 
     # ---- frame-range sharding of one stream (extension; include/lamejs_hip.h: lhip_seek / lhip_state_get / lhip_state_set) ----
     def seek_tail_samples(self) -> int:
-        self._lib.lhip_seek_tail_samples.restype = ctypes.c_size_t
-        self._lib.lhip_seek_tail_samples.argtypes = [ctypes.c_void_p]
         return int(self._lib.lhip_seek_tail_samples(self._h))
 
     def seek(self, sample_pos: int, tail_left, tail_right=None) -> None:
@@ -265,18 +273,14 @@ class Mp3Encoder:
             raise ValueError("seek: a two-channel stream needs both tails")
         r = l if self.channels == 1 else _as_i16(tail_right)
         assert len(l) == self.seek_tail_samples() == len(r)
-        self._lib.lhip_seek.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
         rc = self._lib.lhip_seek(self._h, int(sample_pos), l.ctypes.data, r.ctypes.data)
         if rc != 0:
             raise LhipError(f"lhip_seek failed ({rc}): {self._lib.lhip_last_error().decode()}")
 
     def state_get(self) -> bytes:
         """The complete carried state of the stream (host counters + device record): equal blobs = equal futures."""
-        self._lib.lhip_state_bytes.restype = ctypes.c_size_t
-        self._lib.lhip_state_bytes.argtypes = [ctypes.c_void_p]
         n = int(self._lib.lhip_state_bytes(self._h))
         buf = ctypes.create_string_buffer(n)
-        self._lib.lhip_state_get.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
         rc = self._lib.lhip_state_get(self._h, buf, n)
         if rc != 0:
             raise LhipError(f"lhip_state_get failed ({rc}): {self._lib.lhip_last_error().decode()}")
@@ -284,7 +288,6 @@ class Mp3Encoder:
 
     def state_set(self, blob: bytes) -> None:
         buf = ctypes.create_string_buffer(blob, len(blob))
-        self._lib.lhip_state_set.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
         rc = self._lib.lhip_state_set(self._h, buf, len(blob))
         if rc != 0:
             raise LhipError(f"lhip_state_set failed ({rc}): {self._lib.lhip_last_error().decode()}")

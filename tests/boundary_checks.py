@@ -21,11 +21,6 @@ def run_boundary_checks(lib, oracle_encode):
     import lamejs_amd
     import pcm
 
-    lib.lhip_flush_batch.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.lhip_encode_batch.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.lhip_state_get.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-    lib.lhip_state_bytes.restype = ctypes.c_size_t
-    lib.lhip_state_bytes.argtypes = [ctypes.c_void_p]
     for ch, sr, kbps, resv in ((2, 44100, 128, False), (1, 22050, 64, False), (1, 44100, 128, True)):
         nfr = 9
         L, R = pcm.bursts(1152 * nfr + 300, ch, seed=4100 + ch)

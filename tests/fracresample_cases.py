@@ -2,15 +2,15 @@
 tests/tools/gen_golden_fracresample.js from the unmodified reference) driven through the C ABI -- the HIP library or a simulation of it."""
 import ctypes
 import hashlib
-import json
 
 import numpy as np
 
-from conftest import ROOT, load_case_pcm
+import golden_cases
+from conftest import load_case_pcm
 
 
 def golden_frac():
-    return json.loads((ROOT / "tests" / "golden" / "golden_fracresample.json").read_text())
+    return golden_cases.load("golden_fracresample")
 
 
 def triples(cases):
@@ -29,16 +29,12 @@ def frames_of(data: bytes, lengths):
 def predict(lib, enc, nsamples):
     """(k, frames, rc) of the next call by the host arithmetic alone"""
     k, f = ctypes.c_int32(), ctypes.c_int32()
-    lib.lhip_debug_frac_call.restype = ctypes.c_int
-    lib.lhip_debug_frac_call.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     rc = lib.lhip_debug_frac_call(enc._h, nsamples, ctypes.byref(k), ctypes.byref(f))
     return k.value, f.value, rc
 
 
 def predict_flush(lib, enc):
     b, c = (ctypes.c_int32 * 16)(), (ctypes.c_int32 * 16)()
-    lib.lhip_debug_frac_flush.restype = ctypes.c_int
-    lib.lhip_debug_frac_flush.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
     n = lib.lhip_debug_frac_flush(enc._h, b, c, 16)
     assert 0 <= n <= 16
     return [(b[i], bool(c[i])) for i in range(n)]

@@ -4,7 +4,6 @@ reference's bytes; the random family is checked against the unchanged oracle on 
 here in numpy with the reference's roundings (``premix``).  The oracle takes Int16 only, so the family draws its samples such that every
 value behind gains and mix is a whole number inside the Int16 range (``family_pcm``): the roundings themselves -- the preset's 0.95 on the
 left samples only, fractional Float32 input -- are pinned by the goldens."""
-import ctypes
 import hashlib
 import json
 
@@ -12,13 +11,14 @@ import numpy as np
 
 import pcm
 from conftest import ROOT
+from golden_cases import check_stream, feed_calls, load, pinned
 from pcmformats_cases import F32, INTER, S16, encode_fmt, float_pcm
 
 FORMATS = (S16, S16 | INTER, F32, F32 | INTER)
 
 
 def goldens():
-    return json.loads((ROOT / "tests" / "golden" / "golden_inputmix.json").read_text())["cases"]
+    return load("golden_inputmix")["cases"]
 
 
 def case_opts(c):
@@ -40,12 +40,7 @@ def case_pcm(c):
         L, R = ((a >> 2) & ~1).astype(np.int16), ((b >> 2) & ~3).astype(np.int16)
     else:
         L, R = np.asarray(A, dtype=np.int16), (np.asarray(B, dtype=np.int16) if c["channels"] == 2 else None)
-    h = hashlib.md5()
-    h.update(L.tobytes())
-    if R is not None:
-        h.update(R.tobytes())
-    assert h.hexdigest() == c["pcm_md5"], "PCM drifted from the golden generator's"
-    return L, R
+    return pinned((L, R), c["pcm_md5"])
 
 
 def make_encoder(lib, c, **kw):
@@ -53,25 +48,15 @@ def make_encoder(lib, c, **kw):
     return lamejs_amd.Mp3Encoder(c["channels"], c["samplerate"], c["kbps"], lib=lib, fractional_resample=bool(c.get("frac")), **case_opts(c), **kw)
 
 
-def check_against_golden(c, parts, flush):
-    assert [len(p) for p in parts] == c["call_bytes"], (c["name"], [len(p) for p in parts], c["call_bytes"])
-    assert hashlib.md5(b"".join(parts)).hexdigest() == c["enc_md5"], c["name"]
-    assert len(flush) == c["flush_len"], c["name"]
-    if not c["name"].endswith("_frac"):      # (a non-integer-ratio stream's flush frames are silent stand-ins of equal length by design: include/lamejs_hip.h)
-        assert hashlib.md5(flush).hexdigest() == c["flush_md5"], c["name"]
-
-
 def run_golden_case(lib, c, fmt_of_call=None):
     """Every call and the flush of a golden case through lhip_encode_pcm; fmt_of_call(i): the call's layout bit (the sample type is the case's)."""
     L, R = case_pcm(c)
     enc = make_encoder(lib, c)
     try:
-        p, parts = 0, []
-        for i, n in enumerate(c["call_lens"]):
-            fmt = (F32 if c["kind"] == "f32" else S16) | (fmt_of_call(i) if fmt_of_call else 0)
-            parts.append(encode_fmt(lib, enc, fmt, L[p:p + n], None if R is None else R[p:p + n]))
-            p += n
-        check_against_golden(c, parts, enc.flush())
+        kind = F32 if c["kind"] == "f32" else S16
+        parts = feed_calls(c["call_lens"], L, R, lambda i, l, r: encode_fmt(lib, enc, kind | (fmt_of_call(i) if fmt_of_call else 0), l, r))
+        # (a non-integer-ratio stream's flush frames are silent stand-ins of equal length by design: include/lamejs_hip.h)
+        check_stream(c, parts, enc.flush(), flush_md5=not c["name"].endswith("_frac"))
     finally:
         enc.close()
 
@@ -119,31 +104,12 @@ def oracle_bytes(channels_out, samplerate, kbps, lens, L, R, frac=False):
     """The unchanged oracle on a blob built with scale: 1, fed whole-number Float32 planes as Int16, call by call, then its flush (not for
     non-integer ratios: it aborts there by design)."""
     import lamejs_amd
-    from oracle_py import _load
-    lib = _load()
+    from oracle_py import oracle_calls
     blob = lamejs_amd.tables_blob(channels_out, samplerate, kbps, fractional_resample=frac, scale=1.0)
-    buf = ctypes.create_string_buffer(blob, len(blob))
-    h = lib.lo_create(buf, len(blob))
-    assert h
     l16 = np.ascontiguousarray(L, dtype=np.int16)
-    r16 = l16 if R is None else np.ascontiguousarray(R, dtype=np.int16)
+    r16 = None if R is None else np.ascontiguousarray(R, dtype=np.int16)
     assert np.array_equal(l16.astype(np.float32), L) and (R is None or np.array_equal(r16.astype(np.float32), R)), "premix is not whole Int16 numbers"
-    out = np.empty(sum(lens) * 2 + 65536, dtype=np.uint8)
-    parts, p = [], 0
-    try:
-        for n in lens:
-            w = lib.lo_encode(h, l16[p:].ctypes.data, r16[p:].ctypes.data, n, out.ctypes.data, len(out))
-            assert w >= 0
-            parts.append(out[:w].tobytes())
-            p += n
-        fl = b""
-        if not frac:
-            w = lib.lo_flush(h, out.ctypes.data, len(out))
-            assert w >= 0
-            fl = out[:w].tobytes()
-    finally:
-        lib.lo_destroy(h)
-    return parts, fl
+    return oracle_calls(blob, l16, r16, lens, flush=not frac)
 
 
 # ---- the seeded random family ----

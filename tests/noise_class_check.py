@@ -1,7 +1,6 @@
 """TEST helper (CPU tier: host simulation; GPU tier: the device): calc_noise's logarithm-free band classification
 (lamejs_amd/csrc/lhip_math.h noise_class) must agree with the class the reference derives from log10 -- from the f64 value for a
 band evaluated in the call and from the Float32 copy for a cached band -- wherever it does not ask for the logarithm (-1)."""
-import ctypes
 
 import numpy as np
 
@@ -24,7 +23,6 @@ def noise_class_cases(n=400000, seed=5):
 
 
 def check_noise_class(lib):
-    lib.lhip_debug_math.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     x = np.ascontiguousarray(noise_class_cases(), dtype=np.float64)
     out = np.empty_like(x)
     assert lib.lhip_debug_math(9, x.ctypes.data, out.ctypes.data, len(x)) == 0
@@ -46,7 +44,6 @@ def check_div_by_f32(lib, n=600000, seed=11):
     """calc_noise divides every band's noise by xmin (a Float32) through xmin's reciprocal (lhip_math.h div_by_f32: a multiply and two fma);
     the result must be the division's, bit for bit: random operands over the whole range the path can see, divisors down to Float32
     subnormals, quotients next to powers of two, noise = 0."""
-    lib.lhip_debug_math.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     rng = np.random.default_rng(seed)
     a = np.concatenate([10.0 ** rng.uniform(-180, 25, n), rng.uniform(0, 4, n // 4), np.zeros(16), 2.0 ** rng.integers(-300, 60, n // 8).astype(np.float64)])
     b = np.concatenate([10.0 ** rng.uniform(-44.9, 38, n), rng.uniform(0.5, 2, n // 4).astype(np.float32).astype(np.float64), 10.0 ** rng.uniform(-10, 10, 16),
@@ -68,7 +65,6 @@ def check_ma_index(lib, n=400000, seed=13):
     """mask_add's table index ToInt32(log10(ratio) * 16) without the logarithm (k_psy.h ma_index16, v_log_f32 behind it on the device): wherever
     the shortcut answers it must be the logarithm's index -- random ratios over the range the psychoacoustic model produces and every step
     10^(k / 16) approached from both sides down to one ulp."""
-    lib.lhip_debug_math.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     rng = np.random.default_rng(seed)
     xs = [10.0 ** rng.uniform(0, 2, n), 1.0 + rng.uniform(0, 1e-3, n // 4), 10.0 ** rng.uniform(0, 6, n // 4)]
     k = np.arange(0, 97, dtype=np.float64)

@@ -36,46 +36,81 @@ def _load():
     if _lib is None:
         _make_current()          # before the first load: the process keeps the handle it loads
         lib = ctypes.CDLL(str(_SO))
-        lib.lo_create.restype = ctypes.c_void_p
-        lib.lo_create.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-        lib.lo_destroy.argtypes = [ctypes.c_void_p]
-        lib.lo_encode.restype = ctypes.c_long
-        lib.lo_encode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
-        lib.lo_flush.restype = ctypes.c_long
-        lib.lo_flush.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        for name, restype, argtypes in (("lo_create", vp, [vp, sz]), ("lo_destroy", None, [vp]), ("lo_encode", ctypes.c_long, [vp, vp, vp, sz, vp, sz]),
+                                        ("lo_flush", ctypes.c_long, [vp, vp, sz]), ("lo_enable_tap", None, [vp]), ("lo_get_tap", vp, [vp]),
+                                        ("lo_tap_size", sz, []), ("lo_math", None, [ctypes.c_int, vp, vp, sz])):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
     return _lib
+
+
+class OracleStream:
+    """One oracle encoder on a table blob -- the only driver of lo_create / lo_encode / lo_flush / lo_destroy.  Samples are converted to Int16
+    here; ``right=None`` (always, for a one-channel blob) hands the left plane over twice; every call gets an output buffer of
+    ``(n // 1152 + 8) * 1500 + 16384`` bytes (no frame of any configuration exceeds 1441 bytes per 1152 samples); a negative return
+    raises, naming the call.  ``tap=True``: the stage taps of oracle/lo_common.h are recorded, ``tap()`` returns the last frame's."""
+
+    def __init__(self, blob, tap=False):
+        self._lib = _load()
+        buf = ctypes.create_string_buffer(blob, len(blob))
+        self._h = self._lib.lo_create(buf, len(blob))
+        if not self._h:
+            raise RuntimeError("lo_create failed")
+        self._calls = 0
+        if tap:
+            self._lib.lo_enable_tap(self._h)
+
+    def _out(self, what, n, call):
+        out = np.empty((n // 1152 + 8) * 1500 + 16384, dtype=np.uint8)
+        w = call(out.ctypes.data, len(out))
+        if w < 0:
+            raise RuntimeError(f"{what} (call {self._calls}): {w}")
+        self._calls += 1
+        return out[:w].tobytes()
+
+    def encode(self, left, right=None) -> bytes:
+        L = np.ascontiguousarray(left, dtype=np.int16)
+        R = L if right is None else np.ascontiguousarray(right, dtype=np.int16)
+        assert len(R) == len(L)
+        return self._out("lo_encode", len(L), lambda out, cap: self._lib.lo_encode(self._h, L.ctypes.data, R.ctypes.data, len(L), out, cap))
+
+    def flush(self) -> bytes:
+        return self._out("lo_flush", 0, lambda out, cap: self._lib.lo_flush(self._h, out, cap))
+
+    def tap(self) -> bytes:
+        """The lo_tap record of the frame the last call completed (tests/stage_taps.py: TAP)."""
+        return ctypes.string_at(self._lib.lo_get_tap(self._h), self._lib.lo_tap_size())
+
+    def close(self):
+        if self._h:
+            self._lib.lo_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def oracle_calls(blob, L, R, lens, flush=True):
+    """The stream cut into calls of ``lens`` samples -> (bytes per call, flush bytes; b"" without a flush)."""
+    with OracleStream(blob) as o:
+        parts, p = [], 0
+        for n in lens:
+            parts.append(o.encode(L[p:p + n], None if R is None else R[p:p + n]))
+            p += n
+        return parts, (o.flush() if flush else b"")
 
 
 def oracle_encode(channels, samplerate, kbps, left, right=None, chunk=None, flush=True, joint=False, reservoir=False) -> bytes:
     sys.path.insert(0, str(ROOT))
     from lamejs_amd import tables_blob
 
-    lib = _load()
-    blob = tables_blob(channels, samplerate, kbps, joint, reservoir)
-    buf = ctypes.create_string_buffer(blob, len(blob))
-    h = lib.lo_create(buf, len(blob))
-    if not h:
-        raise RuntimeError("lo_create failed")
-    L = np.ascontiguousarray(left, dtype=np.int16)
-    R = L if (channels == 1 or right is None) else np.ascontiguousarray(right, dtype=np.int16)
-    n = len(L)
+    n = len(left)
     chunk = chunk or max(n, 1)
-    cap = (n // 1152 + 8) * 1500 + 16384
-    out = np.empty(cap, dtype=np.uint8)
-    off = 0
-    try:
-        for p in range(0, n, chunk):
-            m = min(chunk, n - p)
-            w = lib.lo_encode(h, L[p:].ctypes.data, R[p:].ctypes.data, m, out[off:].ctypes.data, cap - off)
-            if w < 0:
-                raise RuntimeError(f"lo_encode {w}")
-            off += w
-        if flush:
-            w = lib.lo_flush(h, out[off:].ctypes.data, cap - off)
-            if w < 0:
-                raise RuntimeError(f"lo_flush {w}")
-            off += w
-    finally:
-        lib.lo_destroy(h)
-    return out[:off].tobytes()
+    parts, tail = oracle_calls(tables_blob(channels, samplerate, kbps, joint, reservoir), left, None if channels == 1 else right,
+                               [min(chunk, n - p) for p in range(0, n, chunk)], flush)
+    return b"".join(parts) + tail

@@ -18,7 +18,6 @@ calls (its one-frame calls are tests/test_fracresample_*.py).
 
 Material is tests/tools/fuzz_gpu.material under fixed seeds (SEED + the case's index).  ``census_ok`` states what the material of each
 two-channel family must contain, read from the ORACLE's bytes by tests/sideinfo.py; the CPU tier checks it with every count >= 2."""
-import ctypes
 import json
 import os
 import subprocess
@@ -159,21 +158,9 @@ def oracle_blob(c):
 
 def oracle_stream(blob, L, R):
     """The oracle on this blob: all samples in one call, then its flush (any chunking gives the same stream)."""
-    from oracle_py import _load
-    lib = _load()
-    buf = ctypes.create_string_buffer(blob, len(blob))
-    h = lib.lo_create(buf, len(blob))
-    assert h, "lo_create failed"
-    R = L if R is None else R
-    out = np.empty(len(L) * 2 + 65536, dtype=np.uint8)
-    try:
-        w = lib.lo_encode(h, L.ctypes.data, R.ctypes.data, len(L), out.ctypes.data, len(out))
-        assert w >= 0
-        w2 = lib.lo_flush(h, out[w:].ctypes.data, len(out) - w)
-        assert w2 >= 0
-    finally:
-        lib.lo_destroy(h)
-    return out[:w + w2].tobytes()
+    from oracle_py import oracle_calls
+    (part,), tail = oracle_calls(blob, L, R, [len(L)])
+    return part + tail
 
 
 def case_streams(c):

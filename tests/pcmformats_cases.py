@@ -2,13 +2,13 @@
 planar / interleaved).  Float PCM is derived from the Int16 corpora by exact dyadic arithmetic, bit-identical to
 tests/tools/gen_golden_floatpcm.js; the goldens are the unmodified reference's bytes for Float32Array input."""
 import ctypes
-import hashlib
 import json
 
 import numpy as np
 
 import pcm
 from conftest import ROOT
+from golden_cases import check_stream, feed_calls, load, pinned
 
 S16, F32, INTER = 0, 1, 2
 FORMATS = {"s16_planar": S16, "s16_interleaved": S16 | INTER, "f32_planar": F32, "f32_interleaved": F32 | INTER}
@@ -17,7 +17,7 @@ KINDS = ("frac", "unit", "hot", "ints")
 
 
 def golden_floatpcm():
-    return json.loads((ROOT / "tests" / "golden" / "golden_floatpcm.json").read_text())["cases"]
+    return load("golden_floatpcm")["cases"]
 
 
 def float_pcm(kind, corpus, a, right=False):
@@ -42,11 +42,7 @@ def case_pcm(case):
     A, B = pcm.CORPORA[case["corpus"]](case["nsamples"], case["channels"])
     L = float_pcm(case["kind"], case["corpus"], A)
     R = float_pcm(case["kind"], case["corpus"], B, True) if case["channels"] == 2 else None
-    h = hashlib.md5()
-    h.update(L.tobytes())
-    if R is not None:
-        h.update(R.tobytes())
-    assert h.hexdigest() == case["pcm_md5"], "float PCM drifted from the golden generator's"
+    pinned((L, R), case["pcm_md5"])
     return L, R, A, B
 
 
@@ -100,24 +96,12 @@ def run_golden_case(lib, case, fmt=F32):
     L, R, _, _ = case_pcm(case)
     enc = make_encoder(lib, case)
     try:
-        p, got = 0, []
-        for c, n in enumerate(case["call_lens"]):
-            b = encode_fmt(lib, enc, fmt, L[p:p + n], None if R is None else R[p:p + n])
-            p += n
-            if not case["reservoir"]:      # (with the bit reservoir a call's byte count depends on when the library hands over finished frames)
-                assert len(b) == case["call_bytes"][c], (case["kind"], case["name"], c, len(b), case["call_bytes"][c])
-            got.append(b)
-        f = enc.flush()
-        assert len(b"".join(got)) + len(f) == sum(case["call_bytes"]) + case["flush_len"], (case["kind"], case["name"])
-        if case["frac"]:
-            # a non-integer-ratio stream: the flush frames the reference makes of its own NaN samples are silent stand-ins of equal length by
-            # design (include/lamejs_hip.h; tests/test_fracresample_*.py): calls exact, flush by length
-            assert hashlib.md5(b"".join(got)).hexdigest() == case["enc_md5"] and len(f) == case["flush_len"], (case["kind"], case["name"])
-        elif case["reservoir"]:
-            assert hashlib.md5(b"".join(got) + f).hexdigest() == case["all_md5"], (case["kind"], case["name"])
-        else:
-            assert hashlib.md5(b"".join(got)).hexdigest() == case["enc_md5"], (case["kind"], case["name"])
-            assert hashlib.md5(f).hexdigest() == case["flush_md5"], (case["kind"], case["name"])
+        parts = feed_calls(case["call_lens"], L, R, lambda i, l, r: encode_fmt(lib, enc, fmt, l, r))
+        # with the bit reservoir a call's byte count depends on when the library hands over finished frames: the stream is judged whole.  A
+        # non-integer-ratio stream: the flush frames the reference makes of its own NaN samples are silent stand-ins of equal length by design
+        # (include/lamejs_hip.h; tests/test_fracresample_*.py): calls exact, flush by length
+        resv = bool(case["reservoir"])
+        check_stream(case, parts, enc.flush(), call_bytes=not resv, enc_md5=not resv, flush_md5=not resv and not case["frac"], all_md5=resv)
     finally:
         enc.close()
 

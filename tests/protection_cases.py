@@ -3,14 +3,12 @@ bits.  Two independent yardsticks: the unmodified reference's bytes (tests/golde
 and the CRC-16 of ISO 11172-3 computed here bit by bit (``iso_crc``) over every frame the code under test produced.  The flag bits alone are
 also checked against the unchanged oracle, which reads them from the blob."""
 import ctypes
-import hashlib
-import json
 import struct
 
 import numpy as np
 
 import pcm
-from conftest import ROOT
+from golden_cases import check_stream, feed_calls, load, pinned
 
 BR1 = [0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320]
 BR2 = [0, 8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160]
@@ -18,7 +16,7 @@ SR = {3: [44100, 48000, 32000], 2: [22050, 24000, 16000], 0: [11025, 12000, 8000
 
 
 def goldens():
-    return json.loads((ROOT / "tests" / "golden" / "golden_protection.json").read_text())["cases"]
+    return load("golden_protection")["cases"]
 
 
 def case_opts(c):
@@ -27,13 +25,7 @@ def case_opts(c):
 
 
 def case_pcm(c):
-    L, R = pcm.CORPORA[c["corpus"]](c["nsamples"], c["channels"])
-    h = hashlib.md5()
-    h.update(L.tobytes())
-    if R is not None:
-        h.update(R.tobytes())
-    assert h.hexdigest() == c["pcm_md5"], "PCM drifted from the golden generator's"
-    return L, R
+    return pinned(pcm.CORPORA[c["corpus"]](c["nsamples"], c["channels"]), c["pcm_md5"])
 
 
 def make_encoder(lib, c, **kw):
@@ -97,10 +89,7 @@ def check_flags(mp3, c):
 
 def check_against_golden(c, parts, flush, calls=True):
     """parts: the bytes of the encode calls (any chunking of the case's samples gives the same stream); calls: they were the case's own calls."""
-    if calls:
-        assert [len(p) for p in parts] == c["call_bytes"], (c["name"], [len(p) for p in parts], c["call_bytes"])
-    assert hashlib.md5(b"".join(parts)).hexdigest() == c["enc_md5"], c["name"]
-    assert len(flush) == c["flush_len"] and hashlib.md5(flush).hexdigest() == c["flush_md5"], c["name"]
+    check_stream(c, parts, flush, call_bytes=calls)
     whole = b"".join(parts) + flush
     assert check_crc(whole, c.get("protect")) == c["frames"], c["name"]
     check_flags(whole, c)
@@ -112,11 +101,8 @@ def run_golden_case(lib, c, lens=None):
     L, R = case_pcm(c)
     enc = make_encoder(lib, c)
     try:
-        p, parts = 0, []
-        for n in (lens or c["call_lens"]):
-            parts.append(enc.encodeBuffer(L[p:p + n], None if R is None else R[p:p + n]))
-            p += n
-        assert p == c["nsamples"]
+        assert sum(lens or c["call_lens"]) == c["nsamples"]
+        parts = feed_calls(lens or c["call_lens"], L, R, lambda i, l, r: enc.encodeBuffer(l, r))
         return check_against_golden(c, parts, enc.flush(), calls=lens is None)
     finally:
         enc.close()
@@ -175,29 +161,13 @@ def flag_family(seed, count, max_frames=5):
 
 def flag_family_check(lib, cases):
     import lamejs_amd
-    from oracle_py import _load
-    olib = _load()
+    from oracle_py import oracle_calls
     for fc in cases:
         ch, sr, kb, joint = fc["cfg"]
         L, R = pcm.CORPORA[("centre_" if joint else "") + fc["corpus"]](fc["n"], ch, fc["seed"])
-        blob = lamejs_amd.tables_blob(ch, sr, kb, joint=joint, **fc["flags"])
-        buf = ctypes.create_string_buffer(blob, len(blob))
-        h = olib.lo_create(buf, len(blob))
-        assert h
-        l16 = np.ascontiguousarray(L, dtype=np.int16)
-        r16 = l16 if R is None else np.ascontiguousarray(R, dtype=np.int16)
-        out = np.empty(fc["n"] * 2 + 65536, dtype=np.uint8)
-        want = b""
-        try:
-            for p in range(0, fc["n"], fc["chunk"]):
-                w = olib.lo_encode(h, l16[p:].ctypes.data, r16[p:].ctypes.data, min(fc["chunk"], fc["n"] - p), out.ctypes.data, len(out))
-                assert w >= 0
-                want += out[:w].tobytes()
-            w = olib.lo_flush(h, out.ctypes.data, len(out))
-            assert w >= 0
-            want += out[:w].tobytes()
-        finally:
-            olib.lo_destroy(h)
+        parts, tail = oracle_calls(lamejs_amd.tables_blob(ch, sr, kb, joint=joint, **fc["flags"]), L, R,
+                                   [min(fc["chunk"], fc["n"] - p) for p in range(0, fc["n"], fc["chunk"])])
+        want = b"".join(parts) + tail
         enc = lamejs_amd.Mp3Encoder(ch, sr, kb, lib=lib, joint=joint, **fc["flags"])
         got = b"".join(enc.encodeBuffer(L[p:p + fc["chunk"]], None if R is None else R[p:p + fc["chunk"]]) for p in range(0, fc["n"], fc["chunk"])) + enc.flush()
         enc.close()

@@ -10,7 +10,7 @@ import ctypes
 
 import numpy as np
 
-from oracle_py import _load as _load_oracle
+from oracle_py import OracleStream
 
 SFBMAX = 39
 TAP = np.dtype([("xr", "<f4", (2, 2, 576)), ("block_type", "<i4", (2, 2)), ("ratio", "<f4", (2, 2, 122)), ("ath_adjust", "<f8"),
@@ -30,30 +30,15 @@ GRSIDE = np.dtype([(f, "<i4") for f in _GRSIDE_FIELDS] + [("scalefac", "<i4", (S
 def oracle_stages(channels, samplerate, kbps, L, R, joint=False):
     """Per-frame taps of the oracle: list of TAP records (one per emitted frame, flush excluded)."""
     import lamejs_amd
-    lib = _load_oracle()
-    lib.lo_enable_tap.argtypes = [ctypes.c_void_p]
-    lib.lo_get_tap.restype = ctypes.c_void_p
-    lib.lo_get_tap.argtypes = [ctypes.c_void_p]
-    lib.lo_tap_size.restype = ctypes.c_size_t
-    assert lib.lo_tap_size() == TAP.itemsize, (lib.lo_tap_size(), TAP.itemsize)
-    blob = lamejs_amd.tables_blob(channels, samplerate, kbps, joint)
-    buf = ctypes.create_string_buffer(blob, len(blob))
-    h = lib.lo_create(buf, len(blob))
-    assert h
-    lib.lo_enable_tap(h)
-    L = np.ascontiguousarray(L, dtype=np.int16)
-    R = L if (channels == 1 or R is None) else np.ascontiguousarray(R, dtype=np.int16)
-    out = np.empty(1 << 16, dtype=np.uint8)
     taps = []
-    # the smallest chunk that never completes two frames in one call (mode_gr = 1 configurations: 576-sample frames)
-    step = 576
-    for p in range(0, len(L), step):
-        m = min(step, len(L) - p)
-        w = lib.lo_encode(h, L[p:].ctypes.data, R[p:].ctypes.data, m, out.ctypes.data, out.size)
-        assert w >= 0
-        if w > 0:
-            taps.append(np.frombuffer(ctypes.string_at(lib.lo_get_tap(h), TAP.itemsize), dtype=TAP)[0].copy())
-    lib.lo_destroy(h)
+    with OracleStream(lamejs_amd.tables_blob(channels, samplerate, kbps, joint), tap=True) as o:
+        # the smallest chunk that never completes two frames in one call (mode_gr = 1 configurations: 576-sample frames)
+        step = 576
+        for p in range(0, len(L), step):
+            if o.encode(L[p:p + step], None if (channels == 1 or R is None) else R[p:p + step]):
+                rec = o.tap()
+                assert len(rec) == TAP.itemsize, (len(rec), TAP.itemsize)
+                taps.append(np.frombuffer(rec, dtype=TAP)[0].copy())
     return taps
 
 

@@ -18,6 +18,25 @@ def test_hip_library_exports_declared_symbols():
     assert b"HIP gfx950" in lib.lhip_version()
 
 
+def test_signature_table_matches_the_header():
+    """lamejs_amd.ABI, the one ctypes declaration of the C ABI, against the prototypes of include/lamejs_hip.h: the same entries, the same
+    parameter counts, and no pointer, size_t or 64-bit parameter or result declared as a C int (ctypes would truncate it)."""
+    import lamejs_amd
+    hdr = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "lamejs_hip.h").read_text(), flags=re.S)
+    protos = {name: (ret, [] if args.strip() == "void" else args.split(","))
+              for ret, name, args in re.findall(r"^([\w \*]+?)\b(lhip_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M)}
+    assert len(protos) >= 30 and set(lamejs_amd.ABI) == set(protos)
+    wide = re.compile(r"\*|\b(size_t|u?int64_t)\b")
+    narrow = (ctypes.c_int, ctypes.c_int32, ctypes.c_uint32, None)
+    for name, (ret, params) in protos.items():
+        restype, argtypes = lamejs_amd.ABI[name]
+        assert len(argtypes) == len(params), (name, len(argtypes), params)
+        assert not (wide.search(ret) and restype in narrow), (name, ret)
+        for text, t in zip(params, argtypes):
+            assert not (wide.search(text) and t in narrow), (name, text.strip())
+            assert wide.search(text) or t is ctypes.c_int, (name, text.strip())
+
+
 def test_debug_last_paths_is_exported_and_mirrored():
     """lhip_debug_last_paths: declared, exported, refuses a null pointer, reports no path before any batch; the mirror's names are the
     header's LHIP_PATH_* bits in order."""
@@ -63,11 +82,8 @@ def test_configs_outside_the_envelope_fail_loudly(golden):
 
 def test_set_devices_argument_handling():
     """lhip_set_devices without a GPU: fails loudly (no device to allow); with one: rejects masks naming absent devices."""
-    import ctypes
     import lamejs_amd
     lib = lamejs_amd.load_library()
-    lib.lhip_set_devices.restype = ctypes.c_int
-    lib.lhip_set_devices.argtypes = [ctypes.c_uint64]
     n = lib.lhip_device_count()
     if n <= 0:
         assert lib.lhip_set_devices(1) < 0 and b"no HIP device" in lib.lhip_last_error()

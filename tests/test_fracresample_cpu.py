@@ -1,10 +1,8 @@
 """{ fractionalResample } (extension): the 49 configurations the reference resamples by a non-integer ratio, call-sequence-exact.
 CPU tier: tables, the unchanged oracle against the goldens of the unmodified reference, the kernel logic (host / wave simulation) and the
 host arithmetic (outputs and frames per call, the flush plan)."""
-import ctypes
 import hashlib
 import json
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,8 +10,8 @@ import pytest
 
 import fracresample_cases as fc
 from conftest import ROOT, load_case_pcm
+from libs import ADDON, HOSTSIM_SO, NODE, run_js_check, sim, wavesim  # noqa: F401
 
-NODE = shutil.which("node")
 RATES = [8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000]
 KBPS = [8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160, 192, 224, 256, 320]
 
@@ -21,24 +19,6 @@ KBPS = [8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160, 192, 224, 256
 @pytest.fixture(scope="module")
 def G():
     return fc.golden_frac()
-
-
-def _sim(name):
-    import lamejs_amd
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
-    lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / name)
-    assert b"HOST SIMULATION" in lib.lhip_version()
-    return lib
-
-
-@pytest.fixture(scope="module")
-def sim():
-    return _sim("liblamejs_hostsim.so")
-
-
-@pytest.fixture(scope="module")
-def wavesim():
-    return _sim("liblamejs_wavesim.so")
 
 
 def test_golden_set_is_the_one_asked_for(G):
@@ -80,9 +60,7 @@ def test_refused_without_the_option_accepted_with_it(G):
 @pytest.mark.skipif(NODE is None, reason="node not available")
 def test_blackfilt_rows_equal_a_live_reference(G):
     """One triple per ratio: all 2 * bpc + 1 windows of the blob against gfc.blackfilt of the unmodified reference after its first call."""
-    r = subprocess.run([NODE, str(ROOT / "tests" / "tools" / "check_fracresample_tables.js")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    res = run_js_check("tools/check_fracresample_tables.js")
     assert res["ratios"] == G["ratios"] and res["mismatches"] == 0 and res["rows"] >= 3 * G["ratios"]
 
 
@@ -90,28 +68,19 @@ def test_unchanged_oracle_reproduces_every_golden_call_sequence(G):
     """Blob + generator without a GPU: the oracle (its fill_buffer_resample works for any ratio from the blob) fed the new blobs and the golden
     call sequences.  Its flush is not called for these configurations (it aborts at the first fractional position by design)."""
     import lamejs_amd
-    from oracle_py import _load
-    lib = _load()
+    from oracle_py import OracleStream
     for case in G["cases"]:
         L, R = load_case_pcm(case)
-        blob = lamejs_amd.tables_blob(case["channels"], case["samplerate"], case["kbps"], fractional_resample=True)
-        buf = ctypes.create_string_buffer(blob, len(blob))
-        h = lib.lo_create(buf, len(blob))
-        assert h
-        out, p, good, got = np.empty(8192, dtype=np.uint8), 0, 0, []
-        try:
+        p, good, got = 0, 0, []
+        with OracleStream(lamejs_amd.tables_blob(case["channels"], case["samplerate"], case["kbps"], fractional_resample=True)) as o:
             for c, n in enumerate(case["call_lens"]):
-                l = fc.np_i16(L[p:p + n])
-                r = l if R is None else fc.np_i16(R[p:p + n])
+                l, r = L[p:p + n], None if R is None else R[p:p + n]
                 p += n
                 if c == case.get("bad_call", -1):
                     continue
-                w = lib.lo_encode(h, l.ctypes.data, r.ctypes.data, n, out.ctypes.data, len(out))
-                assert w == case["call_bytes"][good], (case["channels"], case["samplerate"], case["kbps"], case["kind"], c, w)
-                got.append(out[:w].tobytes())
+                got.append(o.encode(l, r))
+                assert len(got[-1]) == case["call_bytes"][good], (case["channels"], case["samplerate"], case["kbps"], case["kind"], c, len(got[-1]))
                 good += 1
-        finally:
-            lib.lo_destroy(h)
         assert hashlib.md5(b"".join(got)).hexdigest() == case["enc_md5"], (case["channels"], case["samplerate"], case["kbps"], case["kind"])
 
 
@@ -161,13 +130,9 @@ def test_refused_entries_and_option_combinations(sim):
     plain.close()
 
 
-@pytest.mark.skipif(NODE is None or not (ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node").exists(), reason="node / addon not available")
+@pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node / addon not available")
 def test_js_beside_the_live_reference_hostsim(sim):
     """lamejs_amd/js with { fractionalResample: true } (kernel logic: the one-lane simulation) beside the live unmodified reference:
     tests/js_fracresample_check.js, fixed seed."""
-    import os
-    env = dict(os.environ, LAMEJS_HIP_LIB=str(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so"))
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_fracresample_check.js"), "20251"], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    res = run_js_check("js_fracresample_check.js", 20251, lib=HOSTSIM_SO)
     assert res["calls"] == 160 and res["mismatches"] == 0 and res["refused_long_calls"] == 8 and res["clean_flush_frames"] >= 1

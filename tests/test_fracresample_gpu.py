@@ -1,26 +1,10 @@
 """{ fractionalResample } (extension) on the GPU: every golden case of the unmodified reference through the C ABI of the HIP library, the
 batch over all 49 configurations, the refused calls, and lamejs_amd/js beside the live reference under Node.  Reads tests/golden/ and
 oracle/_ref/ only."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
 import fracresample_cases as fc
-from conftest import ROOT
-
-NODE = shutil.which("node")
-ADDON = ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import lamejs_amd
-    lib = lamejs_amd.load_library()
-    assert lib.lhip_device_count() > 0 and b"HOST SIMULATION" not in lib.lhip_version()
-    return lib
+from libs import ADDON, NODE, lib, run_js_check  # noqa: F401
 
 
 @pytest.mark.gpu
@@ -47,7 +31,5 @@ def test_gpu_batch_over_all_49_configurations(lib):
 def test_gpu_js_beside_the_live_reference():
     """lamejs_amd/js with { fractionalResample: true } beside the live unmodified reference on fresh pseudo-random PCM: 8 triples x 20 calls of
     576 samples, encodeBuffer() bytes equal call by call, the flush by the clean / not-clean rule (flags from the live reference)."""
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_fracresample_check.js")], capture_output=True, text=True, env=dict(os.environ))
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    res = run_js_check("js_fracresample_check.js")
     assert res["triples"] == 8 and res["calls"] == 8 * 20 and res["mismatches"] == 0 and res["clean_flush_frames"] >= 1 and res["refused_long_calls"] == 8

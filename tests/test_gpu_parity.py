@@ -9,17 +9,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_case_pcm
+from libs import ADDON, NODE, lib, run_js_check  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import lamejs_amd
-    l = lamejs_amd.load_library()
-    assert l.lhip_device_count() > 0, "no HIP device"
-    assert b"HIP gfx950" in l.lhip_version()
-    return l
 
 
 def _encode(ch, kbps, L, R, chunk, sr=44100, joint=False, reservoir=False):
@@ -62,7 +54,6 @@ def test_device_math_matches_v8(lib):
     including every special-operand branch (op 7: the branch-free log10 of the quantizer on its domain, x >= 2^-1022 | inf | NaN)."""
     import oracle_py
     o = oracle_py._load()
-    o.lo_math.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     for op, x in _math_cases().items():
         x = np.ascontiguousarray(x, dtype=np.float64)
         n = len(x)
@@ -400,7 +391,6 @@ def test_gpu_seed_repair_path(lib, sr, kbps):
     from oracle_py import oracle_encode
     L, R = pcm.bursts(1152 * 40, 2, seed=78)
     want = oracle_encode(2, sr, kbps, L, R)
-    lib.lhip_debug_set_spec_seed.argtypes = [ctypes.c_int, ctypes.c_int]
     try:
         assert lib.lhip_debug_set_spec_seed(255, 1) == 0
         enc = lamejs_amd.Mp3Encoder(2, sr, kbps)
@@ -521,8 +511,6 @@ def test_gpu_async_batch_and_device_mask(lib):
         assert hip.hipMalloc(ctypes.byref(p), n) == 0
         return p
 
-    lib.lhip_set_devices.restype = ctypes.c_int
-    lib.lhip_set_devices.argtypes = [ctypes.c_uint64]
     assert lib.lhip_set_devices(1) == 1
     bufs = []
     try:
@@ -715,10 +703,6 @@ def test_gpu_two_devices_round_robin_and_concurrent_batches(lib):
     if aliased:         # one GPU: ordinals 0 and 1 become two SEPARATE library contexts (mutex, HIP stream, workspaces, table uploads) on it (lhip_rt.h rt::alias_n)
         os.environ["LHIP_ALIAS_DEVICES"] = "2"
         assert lib.lhip_device_count() == 2
-    lib.lhip_set_devices.restype = ctypes.c_int
-    lib.lhip_set_devices.argtypes = [ctypes.c_uint64]
-    lib.lhip_stream_device.restype = ctypes.c_int
-    lib.lhip_stream_device.argtypes = [ctypes.c_void_p]
     assert lib.lhip_set_devices(0b11) == 2
     try:
         encs = [lamejs_amd.Mp3Encoder(2, 44100, 128) for _ in range(6)]
@@ -844,16 +828,12 @@ def test_gpu_host_call_in_overlapped_chunks(lib, tmp_path):
         b = enc.encodeBuffer(L[:extra], R[:extra])                   # an ordinary batch on the same stream
         got[name] = a + b + enc.flush()
         enc.close()
-    node = shutil.which("node")
     js = None
-    if node and (ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node").exists():
+    if NODE and ADDON.exists():
         L, R = mats["joint"]
         np.concatenate([L, L[:extra]]).astype("<i2").tofile(tmp_path / "l.s16")
         np.concatenate([R, R[:extra]]).astype("<i2").tofile(tmp_path / "r.s16")
-        r = subprocess.run([node, str(ROOT / "tests" / "js_hostcall_check.js"), str(tmp_path / "l.s16"), str(tmp_path / "r.s16"), "128", str(len(L)), "joint"],
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        js = __import__("json").loads(r.stdout.strip().splitlines()[-1])
+        js = run_js_check("js_hostcall_check.js", tmp_path / "l.s16", tmp_path / "r.s16", 128, len(L), "joint", timeout=600)
     for name, _, _, _ in cases:
         assert procs[name].wait(timeout=600) == 0
         want = (tmp_path / f"{name}.mp3").read_bytes()

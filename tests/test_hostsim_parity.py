@@ -8,16 +8,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_case_pcm
+from libs import sim  # noqa: F401
 from oracle_py import oracle_encode
-
-
-@pytest.fixture(scope="module")
-def sim():
-    import lamejs_amd
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
-    lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so")
-    assert b"HOST SIMULATION" in lib.lhip_version()
-    return lib
 
 
 def _encode(lib, ch, kbps, L, R, chunk, sr=44100, joint=False, reservoir=False):
@@ -110,7 +102,6 @@ def test_hostsim_seed_repair_path(sim, sr, kbps):
     import lamejs_amd, pcm
     L, R = pcm.bursts(1152 * 12, 2, seed=77)
     want = oracle_encode(2, sr, kbps, L, R)
-    sim.lhip_debug_set_spec_seed.argtypes = [ctypes.c_int, ctypes.c_int]
     try:
         assert sim.lhip_debug_set_spec_seed(255, 1) == 0
         enc = lamejs_amd.Mp3Encoder(2, sr, kbps, lib=sim)
@@ -437,7 +428,6 @@ def test_hostsim_validation_counters_tap(sim):
     steady tone nothing is flagged -- and the bytes are the oracle's either way."""
     import lamejs_amd
     import pcm
-    sim.lhip_debug_set_spec_seed.argtypes = [ctypes.c_int, ctypes.c_int]
     L, R = pcm.sine(1152 * 30, 2, seed=5)
     want = oracle_encode(2, 44100, 128, L, R)
     buf = (ctypes.c_int32 * 64)()

@@ -3,7 +3,6 @@ reference goldens and a random family against the unchanged oracle on the kernel
 lanes), refusals, lhip_seek and the state record."""
 import ctypes
 import json
-import shutil
 import subprocess
 
 import numpy as np
@@ -11,29 +10,11 @@ import pytest
 
 import inputmix_cases as mc
 from conftest import ROOT
+from libs import ADDON, HOSTSIM_SO, NODE, run_js_check, sim, wavesim  # noqa: F401
 from pcmformats_cases import F32, INTER, S16, encode_fmt
 
-NODE = shutil.which("node")
 RATES = [8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000]
 KBPS = [8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160, 192, 224, 256, 320]
-
-
-def _sim(name):
-    import lamejs_amd
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
-    lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / name)
-    assert b"HOST SIMULATION" in lib.lhip_version()
-    return lib
-
-
-@pytest.fixture(scope="module")
-def sim():
-    return _sim("liblamejs_hostsim.so")
-
-
-@pytest.fixture(scope="module")
-def wavesim():
-    return _sim("liblamejs_wavesim.so")
 
 
 @pytest.fixture(scope="module")
@@ -203,12 +184,8 @@ def test_state_does_not_depend_on_the_layout_of_the_calls(sim, G):
         b.close()
 
 
-@pytest.mark.skipif(NODE is None or not (ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node").exists() or not (ROOT / "oracle" / "_ref" / "lame.all.js").exists(),
+@pytest.mark.skipif(NODE is None or not ADDON.exists() or not (ROOT / "oracle" / "_ref" / "lame.all.js").exists(),
                     reason="node / addon / reference bundle not available")
 def test_js_beside_the_live_reference_hostsim():
-    import os
-    env = dict(os.environ, LAMEJS_HIP_LIB=str(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so"))
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_inputmix_check.js"), "20272"], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    res = run_js_check("js_inputmix_check.js", 20272, lib=HOSTSIM_SO)
     assert res["mismatches"] == 0 and res["calls"] == 137 and res["type_errors"] == 2 and set(res["families"]) >= {"downmix", "downmix_interleaved", "gains", "batch", "pending", "fractional"}

@@ -1,8 +1,6 @@
 """Input gains (scale, scale_left, scale_right) and the stereo-to-mono downmix on the GPU: the goldens of the unmodified reference, the
 one-frame program against the batch kernels, a batch of unequal streams, the device-pointer entry, a random family against the oracle and
 the JavaScript wrapper beside the live reference.  Streams of at most 12 frames.  Reads tests/golden/ and oracle/_ref/ only."""
-import json
-import subprocess
 import sys
 
 import numpy as np
@@ -11,15 +9,8 @@ import pytest
 import inputmix_cases as mc
 import pcmformats_cases as pc
 from conftest import ROOT
+from libs import ADDON, NODE, lib, run_check, run_js_check  # noqa: F401
 from pcmformats_cases import F32, INTER, S16
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import lamejs_amd
-    lib = lamejs_amd.load_library()
-    assert lib.lhip_device_count() > 0 and b"HOST SIMULATION" not in lib.lhip_version()
-    return lib
 
 
 @pytest.mark.gpu
@@ -70,9 +61,7 @@ def test_gpu_batch_of_three_unequal_streams(lib):
 @pytest.mark.gpu
 def test_gpu_device_entry_zeroes_and_counts_both_source_channels():
     """In a process of its own (torch initialises the GPU before the library is loaded): inputmix_cases.device_downmix_check."""
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "inputmix_cases.py"), "--device-downmix"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    assert json.loads(r.stdout.strip().splitlines()[-1])["device_downmix_formats"] == 4
+    assert run_check([sys.executable, ROOT / "tests" / "inputmix_cases.py", "--device-downmix"], timeout=300)["device_downmix_formats"] == 4
 
 
 @pytest.mark.gpu
@@ -80,15 +69,8 @@ def test_gpu_random_family_equals_the_oracle(lib):
     assert mc.family_check(lib, mc.family(20273, 10)) == 10
 
 
-NODE = __import__("shutil").which("node")
-ADDON = ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node"
-
-
 @pytest.mark.gpu
 @pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node / addon not available")
 def test_gpu_js_beside_the_live_reference():
-    import os
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_inputmix_check.js"), "90418"], capture_output=True, text=True, env=dict(os.environ), timeout=300)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    res = run_js_check("js_inputmix_check.js", 90418, timeout=300)
     assert res["calls"] == 137 and res["mismatches"] == 0 and res["type_errors"] == 2

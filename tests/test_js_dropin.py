@@ -1,27 +1,13 @@
 """The JavaScript host (lamejs_amd/js: Mp3Encoder + N-API addon) must be a drop-in for the reference API:
 same calls as the reference's Tests.js, same bytes as the goldens.  CPU run uses the host-simulation
 library (logic only); the GPU run uses the real HIP library."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-from conftest import ROOT
-
-NODE = shutil.which("node")
-ADDON = ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node"
+from libs import ADDON, HOSTSIM_SO, NODE, run_js_check
 
 
 def _run(env_lib, corpus, ch, kbps, nfr, chunk, sr=44100, joint=False, reservoir=False):
-    env = dict(os.environ)
-    if env_lib:
-        env["LAMEJS_HIP_LIB"] = str(env_lib)
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_dropin_check.js"), corpus, str(ch), str(kbps), str(nfr), str(chunk), str(sr)] + (["joint"] if joint else []) + (["reservoir"] if reservoir else []),
-                       capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return run_js_check("js_dropin_check.js", corpus, ch, kbps, nfr, chunk, sr, *(["joint"] if joint else []), *(["reservoir"] if reservoir else []), lib=env_lib)
 
 
 def _joint_cases(golden_joint):
@@ -44,9 +30,8 @@ def _cases(golden):
 
 @pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node / addon not available")
 def test_js_dropin_hostsim(golden):
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
     for c in _cases(golden):
-        got = _run(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so", c["corpus"], c["channels"], c["kbps"], c["nsamples"] // 1152, c["chunk"], c.get("samplerate", 44100))
+        got = _run(HOSTSIM_SO, c["corpus"], c["channels"], c["kbps"], c["nsamples"] // 1152, c["chunk"], c.get("samplerate", 44100))
         assert got["md5"] == c["mp3_md5"] and got["bytes"] == c["mp3_len"], c
 
 
@@ -61,9 +46,8 @@ def test_js_dropin_gpu(golden):
 @pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node / addon not available")
 def test_js_joint_stereo_extension_hostsim(golden_joint):
     """new Mp3Encoder(2, sr, kbps, { jointStereo: true }) == the reference core asked for MPEGMode.JOINT_STEREO (golden_joint.json)."""
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
     for c in _joint_cases(golden_joint):
-        got = _run(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so", c["corpus"], 2, c["kbps"], c["nsamples"] // 1152, c["chunk"], c.get("samplerate", 44100), joint=True)
+        got = _run(HOSTSIM_SO, c["corpus"], 2, c["kbps"], c["nsamples"] // 1152, c["chunk"], c.get("samplerate", 44100), joint=True)
         assert got["md5"] == c["mp3_md5"] and got["bytes"] == c["mp3_len"], c
 
 
@@ -77,9 +61,8 @@ def _resv_cases(golden_resv):
 @pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node / addon not available")
 def test_js_bit_reservoir_extension_hostsim(golden_resv):
     """new Mp3Encoder(ch, sr, kbps, { reservoir: true }) == the reference core with gfp.disable_reservoir = false (golden_resv.json)."""
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
     for c in _resv_cases(golden_resv):
-        got = _run(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so", c["corpus"], c["channels"], c["kbps"], c["nsamples"] // 1152, c["chunk"], c.get("samplerate", 44100),
+        got = _run(HOSTSIM_SO, c["corpus"], c["channels"], c["kbps"], c["nsamples"] // 1152, c["chunk"], c.get("samplerate", 44100),
                    joint=bool(c.get("joint")), reservoir=True)
         assert got["md5"] == c["mp3_md5"] and got["bytes"] == c["mp3_len"], c
 
@@ -101,22 +84,14 @@ def test_js_joint_stereo_extension_gpu(golden_joint):
 
 
 def _run_batch(env_lib, ch, kbps, nstreams, nfr, chunk):
-    env = dict(os.environ)
-    if env_lib:
-        env["LAMEJS_HIP_LIB"] = str(env_lib)
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_batch_check.js"), str(ch), str(kbps), str(nstreams), str(nfr), str(chunk)],
-                       capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return run_js_check("js_batch_check.js", ch, kbps, nstreams, nfr, chunk, lib=env_lib)
 
 
 @pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node / addon not available")
 def test_js_batch_extension_hostsim():
     """encodeBatch / flushBatch (many independent streams per launch, BASELINE config 5 shape) == every stream on its own."""
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
-    lib = ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so"
     for ch, kbps, ns, nfr, chunk in ((1, 128, 3, 10, 3000), (2, 128, 2, 6, 1152)):
-        got = _run_batch(lib, ch, kbps, ns, nfr, chunk)
+        got = _run_batch(HOSTSIM_SO, ch, kbps, ns, nfr, chunk)
         assert got["single"] == got["batch"] and len(got["batch"]) == ns
 
 
@@ -129,12 +104,7 @@ def test_js_batch_extension_gpu():
 
 
 def _shard(env_lib, corpus, ch, kbps, nfr, H, cuts):
-    env = dict(os.environ)
-    if env_lib:
-        env["LAMEJS_HIP_LIB"] = str(env_lib)
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_shard_check.js"), corpus, str(ch), str(kbps), str(nfr), str(H)] + [str(c) for c in cuts], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return run_js_check("js_shard_check.js", corpus, ch, kbps, nfr, H, *cuts, lib=env_lib)
 
 
 @pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node / addon not available")
@@ -143,9 +113,8 @@ def test_js_frame_range_shards_hostsim():
     import hashlib
     import pcm
     from oracle_py import oracle_encode
-    sim = ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so"
     for corpus, ch, nfr, H, cuts in (("sine", 2, 40, 8, [14, 27]), ("bursts", 1, 60, 2, [20, 41])):
-        got = _shard(sim, corpus, ch, 128, nfr, H, cuts)
+        got = _shard(HOSTSIM_SO, corpus, ch, 128, nfr, H, cuts)
         L, R = pcm.CORPORA[corpus](1152 * nfr, ch)
         want = oracle_encode(ch, 44100, 128, L, R)
         assert got["whole"] == got["pieces"] == hashlib.md5(want).hexdigest() and got["bytes"] == len(want), got
@@ -161,12 +130,7 @@ def test_js_frame_range_shards_gpu():
 
 
 def _pending(env_lib, corpus, ch):
-    env = dict(os.environ)
-    if env_lib:
-        env["LAMEJS_HIP_LIB"] = str(env_lib)
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_pending_check.js"), corpus, str(ch), "128", "150"], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-2000:]
-    d = json.loads(r.stdout.strip().splitlines()[-1])
+    d = run_js_check("js_pending_check.js", corpus, ch, 128, 150, lib=env_lib)
     for k in ("pending64", "pending7", "pending5_odd_chunks", "pending3_big_chunks"):
         assert d[k]["md5"] == d["plain"]["md5"] and d[k]["bytes"] == d["plain"]["bytes"] and d[k]["second_flush_bytes"] == 0, (k, d)
     assert d["pending64"]["nonempty"] <= 3 < d["plain"]["nonempty"]
@@ -177,7 +141,7 @@ def test_js_pending_frames_extension_hostsim():
     """{ pendingFrames: N } (extension): the 1152-sample call pattern with input held back until N frames are pending -- same byte stream as
     without it, whatever N and whatever the call sizes; flush() returns the rest and a second flush() nothing."""
     for corpus, ch in (("bursts", 2), ("sine", 1)):
-        _pending(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so", corpus, ch)
+        _pending(HOSTSIM_SO, corpus, ch)
 
 
 @pytest.mark.gpu
@@ -193,12 +157,7 @@ def _interleaved(env_lib, nfr):
     import hashlib
     import pcm
     from oracle_py import oracle_encode
-    env = dict(os.environ)
-    if env_lib:
-        env["LAMEJS_HIP_LIB"] = str(env_lib)
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_interleaved_check.js"), str(nfr)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-2000:]
-    d = json.loads(r.stdout.strip().splitlines()[-1])
+    d = run_js_check("js_interleaved_check.js", nfr, lib=env_lib)
     assert d["interleaved"] == d["alone"] and len(d["alone"]) == 7, d
     for name, corpus, ch, kbps, n, seed, kw in (("mono", "sine", 1, 128, 1152 * nfr + 100, 9001, {}), ("stereo", "bursts", 2, 128, 1152 * nfr + 200, 9002, {}),
                                                 ("jr", "bursts", 2, 192, 1152 * nfr + 300, 9006, dict(joint=True, reservoir=True)), ("pend", "sine", 2, 128, 1152 * nfr + 50, 9007, {})):
@@ -209,8 +168,7 @@ def _interleaved(env_lib, nfr):
 
 @pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node / addon not available")
 def test_js_interleaved_live_encoders_hostsim():
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
-    _interleaved(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so", 14)
+    _interleaved(HOSTSIM_SO, 14)
 
 
 @pytest.mark.gpu

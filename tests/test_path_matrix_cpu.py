@@ -5,28 +5,19 @@ expectations, the side-information reader and the path bookkeeping are proven on
   runs: its children are the default environment and the one with both switches;
 * the wave simulation runs the shapes capped at 17 frames, in the default environment (pair program up to 12 frame slots) and with
   LAMEJS_HIP_PAIR_MAX_FRAMES=0 (the persistent workgroup with its tail help at every shape)."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import path_matrix_cases as pm
 import sideinfo
-from conftest import ROOT
+from libs import build_sims, sim_library
 
 
 @pytest.fixture(scope="module")
 def sims():
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
+    build_sims()
     import oracle_py
     oracle_py._make_current()
-
-
-def _sim(name):
-    import lamejs_amd
-    lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / name)
-    assert b"HOST SIMULATION" in lib.lhip_version()
-    return lib
 
 
 def test_case_list_is_the_one_asked_for():
@@ -48,7 +39,7 @@ def test_plan_calls_completes_the_frames_it_plans(sims):
     """The planner against the library's own prediction (lhip_encode_output_bytes is exact without the reservoir): one frame's bytes per
     planned frame, on a resampling LSF stream and an MPEG-1 one."""
     import lamejs_amd
-    lib = _sim("liblamejs_hostsim.so")
+    lib = sim_library("hostsim")
     for c in (pm.cases()[10], pm.cases()[0]):
         C, frame, ratio = pm.cfg_of(c)
         assert (c["family"] == "resample") == (ratio > 1)
@@ -70,7 +61,7 @@ def test_sideinfo_reader_equals_the_device_side_records(sims, cfg):
     from fuzz_gpu import material
     ch, sr, kb, joint = cfg
     L, R = material(np.random.default_rng(77), 1152 * 30, ch)
-    st, mp3 = stage_taps.device_stages(_sim("liblamejs_hostsim.so"), ch, sr, kb, L, R, joint=joint)
+    st, mp3 = stage_taps.device_stages(sim_library("hostsim"), ch, sr, kb, L, R, joint=joint)
     frames = sideinfo.parse(mp3)
     assert len(frames) == st["nframes"] >= 29
     t16 = lambda t: 16 if t == 14 else int(t)

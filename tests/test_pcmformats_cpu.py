@@ -2,32 +2,14 @@
 lhip_encode_batch_device_pcm) -- CPU tier: the kernel bodies in both simulations against the goldens of the unmodified reference
 (Float32Array input, tests/tools/gen_golden_floatpcm.js) and against the unchanged oracle on integer-valued input."""
 import hashlib
-import subprocess
 
 import numpy as np
 import pytest
 
 import pcmformats_cases as pc
-from conftest import ROOT, load_case_pcm
+from conftest import load_case_pcm
+from libs import ADDON, HOSTSIM_SO, NODE, run_js_check, sim, wavesim  # noqa: F401
 from pcmformats_cases import F32, INTER, S16
-
-
-def _sim(name):
-    import lamejs_amd
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
-    lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / name)
-    assert b"HOST SIMULATION" in lib.lhip_version()
-    return lib
-
-
-@pytest.fixture(scope="module")
-def sim():
-    return _sim("liblamejs_hostsim.so")
-
-
-@pytest.fixture(scope="module")
-def wavesim():
-    return _sim("liblamejs_wavesim.so")
 
 
 @pytest.fixture(scope="module")
@@ -252,21 +234,12 @@ def test_python_mirror_dispatches_on_dtype(sim, G):
         e.close()
 
 
-NODE = __import__("shutil").which("node")
-ADDON = ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node"
-
-
 @pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node / addon not available")
 def test_js_beside_the_live_reference_hostsim(sim):
     """lamejs_amd/js on the one-lane simulation beside the live unmodified reference (tests/js_pcmformats_check.js): Float32Array, Float64Array and
     Array with fractional and beyond-16-bit values, Int16Array, encodeInterleaved, encodeBatch with mixed array types and { interleaved },
     a { pendingFrames } encoder that switches from Int16 to Float32 mid-stream, refused samples.  Call by call the reference's bytes -- which
     for Float32Array input are NOT the bytes of Int16Array.from(input), what the drop-in used to encode."""
-    import json
-    import os
-    env = dict(os.environ, LAMEJS_HIP_LIB=str(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so"))
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_pcmformats_check.js"), "20261"], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    res = run_js_check("js_pcmformats_check.js", 20261, lib=HOSTSIM_SO)
     assert res["calls"] == 223 and res["batch_range_errors"] == 1 and res["mismatches"] == 0 and res["range_errors"] == 4 and res["differs_from_int16_coercion"] >= 3
     assert res["families"]["Float32Array"]["calls"] == 52 and 1 <= res["pending_nonempty_calls"] <= 4

@@ -2,8 +2,6 @@
 input), the random family against the oracle in every format on every launch path, device-resident batches per format, and the device
 entry's sanitising.  Reads tests/golden/ and oracle/_ref/ only."""
 import hashlib
-import json
-import subprocess
 import sys
 
 import numpy as np
@@ -11,15 +9,8 @@ import pytest
 
 import pcmformats_cases as pc
 from conftest import ROOT
+from libs import ADDON, NODE, lib, run_check, run_js_check  # noqa: F401
 from pcmformats_cases import F32, INTER, S16
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import lamejs_amd
-    lib = lamejs_amd.load_library()
-    assert lib.lhip_device_count() > 0 and b"HOST SIMULATION" not in lib.lhip_version()
-    return lib
 
 
 @pytest.mark.gpu
@@ -51,9 +42,7 @@ def test_gpu_device_resident_batch(fmt):
     (two channels: about 100 frame slots, g_quant_pair; one channel: g_quant), one frame per stream (g_frame), reservoir streams (g_resv_stream)
     == the oracle (pcmformats_cases.device_batch_check, in a
     process of its own: torch initialises the GPU before the library is loaded)."""
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "pcmformats_cases.py"), "--device-batch", fmt], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    assert json.loads(r.stdout.strip().splitlines()[-1])["device_batches"] == 12
+    assert run_check([sys.executable, ROOT / "tests" / "pcmformats_cases.py", "--device-batch", fmt], timeout=600)["device_batches"] == 12
 
 
 @pytest.mark.gpu
@@ -94,13 +83,7 @@ def test_gpu_host_batch_and_refused_samples(lib):
 @pytest.mark.gpu
 def test_gpu_device_entry_reads_refused_samples_as_zero():
     """Once, in a process and under a time limit of its own (the CPU tier runs the same check on both simulations first)."""
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "pcmformats_cases.py"), "--device-sanitise"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    assert json.loads(r.stdout.strip().splitlines()[-1])["device_sanitise_calls"] == 60
-
-
-NODE = __import__("shutil").which("node")
-ADDON = ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node"
+    assert run_check([sys.executable, ROOT / "tests" / "pcmformats_cases.py", "--device-sanitise"], timeout=600)["device_sanitise_calls"] == 60
 
 
 @pytest.mark.gpu
@@ -108,8 +91,5 @@ ADDON = ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node"
 def test_gpu_js_beside_the_live_reference():
     """lamejs_amd/js on the real library beside the live unmodified reference (tests/js_pcmformats_check.js), fresh seed: every family of
     array types call by call the reference's bytes."""
-    import os
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_pcmformats_check.js"), "90417"], capture_output=True, text=True, env=dict(os.environ), timeout=600)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    res = run_js_check("js_pcmformats_check.js", 90417, timeout=600)
     assert res["calls"] == 223 and res["batch_range_errors"] == 1 and res["mismatches"] == 0 and res["range_errors"] == 4 and res["differs_from_int16_coercion"] >= 3

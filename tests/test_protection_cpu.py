@@ -4,36 +4,17 @@ stored CRC comes from the device function of k_bits.h -- walked by one lane in t
 reduction in the wave simulation.  Yardsticks: the unmodified reference's bytes and a CRC-16 as ISO 11172-3 defines it, written out in
 protection_cases.iso_crc."""
 import json
-import shutil
 import subprocess
 
 import pytest
 
 import protection_cases as pc
 from conftest import ROOT
+from libs import ADDON, HOSTSIM_SO, NODE, run_js_check, sim, wavesim  # noqa: F401
 
-NODE = shutil.which("node")
 RATES = [8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000]
 KBPS = [8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160, 192, 224, 256, 320]
 TABLES_JS = str(ROOT / "lamejs_amd" / "js" / "tables.js")
-
-
-def _sim(name):
-    import lamejs_amd
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
-    lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / name)
-    assert b"HOST SIMULATION" in lib.lhip_version()
-    return lib
-
-
-@pytest.fixture(scope="module")
-def sim():
-    return _sim("liblamejs_hostsim.so")
-
-
-@pytest.fixture(scope="module")
-def wavesim():
-    return _sim("liblamejs_wavesim.so")
 
 
 @pytest.fixture(scope="module")
@@ -235,12 +216,8 @@ def test_seek_and_state_on_a_protected_stream(sim):
         graft.close()
 
 
-@pytest.mark.skipif(NODE is None or not (ROOT / "lamejs_amd" / "js" / "addon" / "lhip_napi.node").exists() or not (ROOT / "oracle" / "_ref" / "lame.all.js").exists(),
+@pytest.mark.skipif(NODE is None or not ADDON.exists() or not (ROOT / "oracle" / "_ref" / "lame.all.js").exists(),
                     reason="node / addon / reference bundle not available")
 def test_js_beside_the_live_reference_hostsim():
-    import os
-    env = dict(os.environ, LAMEJS_HIP_LIB=str(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so"))
-    r = subprocess.run([NODE, str(ROOT / "tests" / "js_protection_check.js"), "20282"], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    res = json.loads(r.stdout.strip().splitlines()[-1])
+    res = run_js_check("js_protection_check.js", 20282, lib=HOSTSIM_SO)
     assert res["mismatches"] == 0 and res["crc_bad"] == 0 and res["range_errors"] == 3 and set(res["families"]) >= {"protect", "flags", "everything", "batch_mixed", "pending"}

@@ -6,14 +6,7 @@ import pytest
 
 import pcm
 import protection_cases as pc
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import lamejs_amd
-    lib = lamejs_amd.load_library()
-    assert lib.lhip_device_count() > 0 and b"HOST SIMULATION" not in lib.lhip_version()
-    return lib
+from libs import lib  # noqa: F401
 
 
 @pytest.fixture(scope="module")

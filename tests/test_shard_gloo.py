@@ -15,7 +15,7 @@ import pcm
 from oracle_py import oracle_encode
 
 ROOT = Path(__file__).resolve().parents[1]
-HOSTSIM = ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so"
+from libs import HOSTSIM_SO as HOSTSIM  # noqa: E402
 
 
 def test_shard_streams_partition():

@@ -2,7 +2,6 @@
 the 64 lanes of a wave running as fibers that meet at every wave primitive (ballots, DPP-style reductions and scans,
 lane broadcasts, the systolic folds -- lhip_wave.h, -DLHIP_WAVESIM).  Unlike the one-lane simulation (test_hostsim_parity.py)
 this executes exactly the lane-parallel code paths the GPU runs; it is ~20 x slower, hence the smaller cases.  Test-only."""
-import ctypes
 import hashlib
 import os
 import subprocess
@@ -11,18 +10,10 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_case_pcm
+from libs import WAVESIM_SO, build_sims, wavesim as wsim  # noqa: F401
 from oracle_py import oracle_encode
 
 FULL = os.environ.get("LAMEJS_WAVESIM_FULL") == "1"      # the long variant (~4 min): goldens up to 110 frames, 16 random cases
-
-
-@pytest.fixture(scope="module")
-def wsim():
-    import lamejs_amd
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
-    lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_wavesim.so")
-    assert b"HOST SIMULATION" in lib.lhip_version()
-    return lib
 
 
 def _encode(lib, ch, kbps, L, R, chunk, sr=44100, joint=False, reservoir=False):
@@ -116,7 +107,6 @@ def test_wavesim_seed_repair_path(wsim):
     import lamejs_amd, pcm
     L, R = pcm.bursts(1152 * 10, 2, seed=77)
     want = oracle_encode(2, 44100, 128, L, R)
-    wsim.lhip_debug_set_spec_seed.argtypes = [ctypes.c_int, ctypes.c_int]
     try:
         assert wsim.lhip_debug_set_spec_seed(255, 1) == 0
         enc = lamejs_amd.Mp3Encoder(2, 44100, 128, lib=wsim)
@@ -167,13 +157,13 @@ def test_wavesim_tail_help():
     are working on.  Two-channel cases in one batch each (plain, joint stereo, MPEG-2) against the oracle,
     and both ways of an offer -- taken by a helper, withdrawn by its owner -- must have been exercised."""
     import sys
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
+    build_sims()
     code = ("import sys; sys.path.insert(0, r'%s'); sys.path.insert(0, r'%s'); sys.path.insert(0, r'%s'); import lamejs_amd, fuzz_gpu\n"
             "lib = lamejs_amd.load_library(r'%s')\n"
             "bad = fuzz_gpu.run(5, 4401, lib=lib, verbose=False, stereo_only=True, whole=True, max_frames=40)\n"
             "bad += fuzz_gpu.run(4, 4402, lib=lib, verbose=False, joint=True, whole=True, max_frames=40)\n"
             "bad += fuzz_gpu.run(4, 4403, lib=lib, verbose=False, cfgs=fuzz_gpu.LSF_CFGS, stereo_only=True, whole=True, max_frames=40)\n"
-            "print('BAD', bad)\n") % (ROOT, ROOT / "tests", ROOT / "tests" / "tools", ROOT / "tests" / "hostsim" / "_build" / "liblamejs_wavesim.so")
+            "print('BAD', bad)\n") % (ROOT, ROOT / "tests", ROOT / "tests" / "tools", WAVESIM_SO)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, LAMEJS_TAILHELP_STATS="1"), timeout=900)
     assert r.returncode == 0 and "BAD []" in r.stdout, (r.stdout[-800:], r.stderr[-1500:])
     import re
@@ -188,7 +178,7 @@ def test_wavesim_one_frame_launch_count_helpers():
     beside the helper's count -- committed, dropped because the evaluation did not fit -- must have occurred; so must a one-channel frame's wait for the
     psyB wave (MPEG-1 mono) and the two-channel barrier path."""
     import sys
-    subprocess.run(["make", "-C", str(ROOT / "tests" / "hostsim"), "all"], check=True, capture_output=True)
+    build_sims()
     code = ("import sys; sys.path.insert(0, r'%s'); sys.path.insert(0, r'%s'); sys.path.insert(0, r'%s'); import numpy as np, lamejs_amd, fuzz_gpu\n"
             "from oracle_py import oracle_encode\n"
             "lib = lamejs_amd.load_library(r'%s')\n"
@@ -199,7 +189,7 @@ def test_wavesim_one_frame_launch_count_helpers():
             "    enc = lamejs_amd.Mp3Encoder(ch, sr, kb, lib=lib, joint=joint, reservoir=resv)\n"
             "    got = b''.join(enc.encodeBuffer(L[p:p + chunk], None if R is None else R[p:p + chunk]) for p in range(0, len(L), chunk)) + enc.flush()\n"
             "    if got != oracle_encode(ch, sr, kb, L, R, joint=joint, reservoir=resv): bad.append((ch, sr, kb, joint, resv))\n"
-            "print('BAD', bad)\n") % (ROOT, ROOT / "tests", ROOT / "tests" / "tools", ROOT / "tests" / "hostsim" / "_build" / "liblamejs_wavesim.so")
+            "print('BAD', bad)\n") % (ROOT, ROOT / "tests", ROOT / "tests" / "tools", WAVESIM_SO)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, LAMEJS_PIPE_STATS="1"), timeout=900)
     assert r.returncode == 0 and "BAD []" in r.stdout, (r.stdout[-800:], r.stderr[-1500:])
     import re

@@ -5,7 +5,6 @@ ROOT = Path(__file__).resolve().parent.parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
 import lamejs_amd, pcm
 lib = lamejs_amd.load_library()
-lib.lhip_kernel_times.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
 for ch in (1, 2):
     L, R = pcm.sine(1152 * 300, ch)
     for frames in (1, 8):

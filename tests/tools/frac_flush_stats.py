@@ -9,8 +9,9 @@ ROOT = Path(__file__).resolve().parent.parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
 import fracresample_cases as fc   # noqa: E402
 import lamejs_amd                  # noqa: E402
+import libs                        # noqa: E402
 
-lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so")
+lib = libs.sim_library("hostsim")
 G = fc.golden_frac()
 print("# kind ch in_rate kbps -> out_rate | calls | flush frames | clean (byte-exact) | NaN frames of the reference | of those byte-equal to the silent stand-in")
 tot = [0, 0, 0, 0]

@@ -103,11 +103,8 @@ def main():
     stereo: two-channel configurations only; whole: every case in ONE encodeBuffer call (one batch of all its frames)
     wavesim: the 64-lane wave programs as fibers on the CPU (slow: use `short`, at most 40 frames per case)"""
     cfgs = LSF_CFGS if "lsf" in sys.argv[3:] else RESAMPLE_CFGS if "resample" in sys.argv[3:] else LOWRATE_CFGS if "lowrate" in sys.argv[3:] else MPEG1_CFGS
-    lib = None
-    if "hostsim" in sys.argv[3:]:
-        lib = lamejs_amd.load_library(str(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_hostsim.so"))
-    if "wavesim" in sys.argv[3:]:
-        lib = lamejs_amd.load_library(str(ROOT / "tests" / "hostsim" / "_build" / "liblamejs_wavesim.so"))
+    import libs
+    lib = libs.sim_library("wavesim") if "wavesim" in sys.argv[3:] else libs.sim_library("hostsim") if "hostsim" in sys.argv[3:] else None
     bad = run(int(sys.argv[1]) if len(sys.argv) > 1 else 60, int(sys.argv[2]) if len(sys.argv) > 2 else 2024, lib=lib, cfgs=cfgs, joint="joint" in sys.argv[3:], reservoir="reservoir" in sys.argv[3:],
               max_frames=40 if "short" in sys.argv[3:] else 260, stereo_only="stereo" in sys.argv[3:], whole="whole" in sys.argv[3:], frame_calls="framecalls" in sys.argv[3:])
     sys.exit(1 if bad else 0)

@@ -45,8 +45,6 @@ _e = mk(VAR["mono_s16"])
 cap = int(lib.lhip_max_output_bytes(_e._h, n))
 _e.close()
 out = torch.zeros(cap, dtype=torch.uint8, device="cuda")
-lib.lhip_kernel_timing.restype = ctypes.c_int
-lib.lhip_kernel_times.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
 
 
 def step(name, timing=False):

@@ -19,6 +19,7 @@ sys.path.insert(0, str(ROOT / "tests"))
 import numpy as np
 
 import lamejs_amd
+import libs
 import path_matrix_cases as pm
 from pcmformats_cases import interleave
 
@@ -33,12 +34,10 @@ def main():
     backend, env_name = sys.argv[1], sys.argv[2]
     t0 = time.time()
     if backend == "gpu":
-        lib = lamejs_amd.load_library()
-        assert lib.lhip_device_count() > 0 and b"HOST SIMULATION" not in lib.lhip_version()
+        lib = libs.gpu_library()
         num_cus = int(sys.argv[3])
     else:
-        lib = lamejs_amd.load_library(ROOT / "tests" / "hostsim" / "_build" / f"liblamejs_{backend}.so")
-        assert b"HOST SIMULATION" in lib.lhip_version()
+        lib = libs.sim_library(backend)
         num_cus = 256                                  # (the simulations' context keeps the default)
     env = {k: os.environ[k] for k in pm.SWITCHES if k in os.environ}
     assert env == pm.ENVS[env_name], (env, env_name)

@@ -43,8 +43,6 @@ if sys.argv[1] == "calls":
 
 F = int(sys.argv[2]) if len(sys.argv) > 2 else 100000
 REPS = int(sys.argv[3]) if len(sys.argv) > 3 else 3
-lib.lhip_kernel_timing.restype = ctypes.c_int
-lib.lhip_kernel_times.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
 t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()      # noqa: E731
 
 
