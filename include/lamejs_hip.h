@@ -55,6 +55,18 @@
  * original, privateBit, emphasis } set the header bits of those names.  lhip_create returns -3 with a message when sideinfo_len does not fit
  * the flag, for a flag that is not 0 or 1, for emphasis 2 (reserved), and for error_protection on a non-integer-ratio stream.
  *
+ * Info tag (extension).  A blob built with { infoTag } (tables.js) makes the stream a FILE: its first call that returns anything -- the first lhip_encode* with
+ * samples, or the flush -- returns, in front of its audio, a placeholder of lhip_stream_info_t::tag_bytes bytes (a valid frame header, then zeros; LAME's
+ * contract), written by the host; the audio behind it is byte for byte the stream without the option, and lhip_max_output_bytes / lhip_encode_output_bytes
+ * count the placeholder while it is pending.  The library keeps the stream's totals on the host -- frames, audio bytes, a 100-point seek table's bag, delay
+ * and end padding -- and the CRC-16 of all audio bytes (the "music CRC": reflected polynomial 0xA001, preset 0), computed where the bytes are: by a kernel
+ * behind the call's last writer for bytes that stay in HBM, by the host for a small call whose bytes arrive in pinned memory anyway.  A device-pointer
+ * batch with such a stream fetches the CRCs at the end of the call, so it synchronises (sync = 0 is ignored).  After lhip_flush, lhip_info_tag writes the
+ * finished tag frame ("Info", frames, bytes, seek table, "LAME3.98r" and LAME's extension fields, music CRC, tag CRC); the caller writes it over the
+ * placeholder at offset 0 of the file.  lhip_create returns -3 with a message where the frame (floor((version + 1) * 72000 * brate / out_samplerate)
+ * bytes) cannot hold sideinfo_len + 156 bytes, and for a stream that resamples by a non-integer ratio.  State blobs do not carry the totals: lhip_info_tag
+ * on a stream moved with lhip_seek or lhip_state_set returns -4.
+ *
  * Semantics preserved: any chunking of the same sample stream yields the same bytes; a call
  * returns the bytes of all whole frames completed by that call (possibly 0); errors are negative
  * return codes mirroring the reference (-1 output buffer too small, -3 bad handle, -4 internal/device
@@ -235,7 +247,32 @@ void lhip_last_batch_stats(int64_t* frames, int64_t* repaired_frames, int64_t* r
 #define LHIP_PATH_FIXUP_SINGLE 0x400u
 #define LHIP_PATH_FIXUP_COOP 0x800u
 #define LHIP_PATH_SMALL_CALL 0x1000u
+/* (one more bit, stated as a shift: OUT_CRC 0x2000 -- the batch held { infoTag } streams and their music CRC was computed by the kernel g_out_crc; such a
+ *  batch without this bit took the host's CRC over the pinned mirror of a SMALL_CALL) */
+#define LHIP_PATH_OUT_CRC (1u << 13)
 int lhip_debug_last_paths(uint32_t* mask);
+
+/* Info tag (extension; see above).  What a stream built with { infoTag } has put out so far, and the finished tag frame. */
+typedef struct lhip_stream_info_t {
+    int64_t frames;        /* audio frames encoded */
+    int64_t audio_bytes;   /* audio bytes returned (the placeholder is not among them) */
+    uint32_t music_crc;    /* CRC-16 of those bytes */
+    int32_t delay;         /* encoder delay in samples (576) */
+    int32_t padding;       /* samples of padding at the end of the stream; -1 before the flush */
+    int32_t tag_bytes;     /* size of the tag frame = of the placeholder */
+} lhip_stream_info_t;
+/* 0, or < 0 with a message (-4: the stream was not built with the option) */
+int lhip_stream_info(const lhip_stream* s, lhip_stream_info_t* info);
+/* Valid after the flush: writes the tag frame to out (capacity cap) and returns its size; -1: cap too small; -4 with a message: not flushed yet, not a
+ * tagged stream, or a stream that was moved with the seek / state entries. */
+int64_t lhip_info_tag(lhip_stream* s, uint8_t* out, size_t cap);
+/* Test hooks.  lhip_debug_crc_span: the bytes one workgroup of the CRC kernel covers.  lhip_debug_crc16: THE KERNEL (in the simulation libraries: its body) over
+ * n bytes of the caller's, placed misalign (0 .. 15) bytes past a 16-byte boundary of device memory -- always the device path, whatever n is; *crc receives
+ * the CRC-16.  lhip_debug_info_toc: the seek table's bookkeeping alone -- ncalls batches of frames[i] frames of kbps each, then the 100 seek points into toc;
+ * returns the number of bag entries in use or < 0. */
+size_t lhip_debug_crc_span(void);
+int lhip_debug_crc16(const void* bytes, size_t n, size_t misalign, uint32_t* crc);
+int lhip_debug_info_toc(const int64_t* frames, size_t ncalls, int kbps, uint8_t* toc);
 
 /* Debug/test taps (tests only): copy intermediate results of the most recent batch to the host.
  * what: 0 xr [granule][ch][576] f32, 1 blocktype [granule][ch] i32, 2 E [granule][psy ch][122] f32 (psy ch = ch, or L R mid side in joint stereo; thresholds

@@ -22,11 +22,13 @@ _PKG = Path(__file__).resolve().parent
 _LIB_PATH = _PKG / "lib" / "liblamejs_hip.so"
 _TABLE_DIR = _PKG / "tables"
 
-__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED", "PATH_NAMES", "last_batch_paths"]
+__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED", "PATH_NAMES", "PATH_NAMES_ALL", "last_batch_paths", "StreamInfo"]
 
 # launch paths of a batch (include/lamejs_hip.h: LHIP_PATH_*), in bit order
 PATH_NAMES = ("FRAME", "FRAME_RESV", "SEPARATE", "PREP", "PSY4", "QUANT_PAIR", "QUANT_PERSISTENT", "RESV_STREAM_HELPERS", "RESV_STREAM_NOHELPERS",
               "RESV_FLUSH", "FIXUP_SINGLE", "FIXUP_COOP", "SMALL_CALL")
+# ... and the bit the header states as a shift: OUT_CRC (the music CRC of ``info_tag`` streams came from the kernel g_out_crc, not from the host)
+PATH_NAMES_ALL = PATH_NAMES + ("OUT_CRC",)
 
 
 def last_batch_paths(lib=None) -> frozenset:
@@ -36,9 +38,9 @@ def last_batch_paths(lib=None) -> frozenset:
     rc = lib.lhip_debug_last_paths(ctypes.byref(m))
     if rc != 0:
         raise LhipError(f"lhip_debug_last_paths failed ({rc}): {lib.lhip_last_error().decode()}")
-    if m.value >> len(PATH_NAMES):
+    if m.value >> len(PATH_NAMES_ALL):
         raise LhipError(f"lhip_debug_last_paths: unknown bits in {m.value:#x}")
-    return frozenset(n for i, n in enumerate(PATH_NAMES) if m.value >> i & 1)
+    return frozenset(n for i, n in enumerate(PATH_NAMES_ALL) if m.value >> i & 1)
 
 
 # sample formats of the *_pcm entries (include/lamejs_hip.h: LHIP_PCM_*): a sample type, optionally or-ed with PCM_INTERLEAVED
@@ -52,6 +54,12 @@ class LhipError(RuntimeError):
 class _Config(ctypes.Structure):
     _fields_ = [("channels", ctypes.c_int32), ("samplerate", ctypes.c_int32), ("kbps", ctypes.c_int32),
                 ("device", ctypes.c_int32)]
+
+
+class StreamInfo(ctypes.Structure):
+    """``lhip_stream_info_t``: what an ``info_tag`` stream has put out so far."""
+    _fields_ = [("frames", ctypes.c_int64), ("audio_bytes", ctypes.c_int64), ("music_crc", ctypes.c_uint32), ("delay", ctypes.c_int32),
+                ("padding", ctypes.c_int32), ("tag_bytes", ctypes.c_int32)]
 
 
 # The C ABI of include/lamejs_hip.h, entry -> (restype, argtypes): the one place that states it.  load_library() applies it to every library it
@@ -95,6 +103,11 @@ ABI = {
     "lhip_frac_call_limit": (_i64, [_ptr]),
     "lhip_debug_frac_call": (_int, [_ptr, _size, _pi32, _pi32]),
     "lhip_debug_frac_flush": (_int, [_ptr, _pi32, _pi32, _int]),
+    "lhip_stream_info": (_int, [_ptr, ctypes.POINTER(StreamInfo)]),
+    "lhip_info_tag": (_i64, [_ptr, _ptr, _size]),
+    "lhip_debug_crc_span": (_size, []),
+    "lhip_debug_crc16": (_int, [_ptr, _size, _size, ctypes.POINTER(ctypes.c_uint32)]),
+    "lhip_debug_info_toc": (_int, [_ptr, _size, _int, _ptr]),
     "lhip_last_error": (ctypes.c_char_p, []),
     "lhip_version": (ctypes.c_char_p, []),
 }
@@ -154,7 +167,7 @@ def _gain_text(g) -> str:
 
 def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, reservoir: bool = False, fractional_resample: bool = False,
                 downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False, copyright: bool = False, original: bool = True,
-                private_bit: bool = False, emphasis: int = 0) -> bytes:
+                private_bit: bool = False, emphasis: int = 0, info_tag: bool = False) -> bytes:
     """The LHTB table blob for a configuration.
 
     Built by the host-side JavaScript ``lamejs_amd/js/tables.js`` (so every transcendental comes
@@ -168,8 +181,10 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     (``{ downmix, scale, scaleLeft, scaleRight }`` of tables.js); without them the blob is the bytes it always was.
     ``protect`` (CRC-protected frames), ``copyright``, ``original``, ``private_bit``, ``emphasis`` (0, 1 or 3): the frame header's settings
     (``{ protect, copyright, original, privateBit, emphasis }`` of tables.js); at their defaults the blob is the bytes it always was.
+    ``info_tag``: the stream starts with the placeholder of an Info/LAME tag frame and keeps the totals the tag reports (``{ infoTag }`` of
+    tables.js: the tag's constants as named entries that exist only with the option); without it the blob is the bytes it always was.
     """
-    for name, v in (("protect", protect), ("copyright", copyright), ("original", original), ("private_bit", private_bit)):
+    for name, v in (("protect", protect), ("copyright", copyright), ("original", original), ("private_bit", private_bit), ("info_tag", info_tag)):
         if v not in (True, False, 0, 1):
             raise ValueError(f"{name} must be True or False")
     if isinstance(emphasis, bool) or emphasis not in (0, 1, 3):
@@ -182,6 +197,7 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     frac = bool(fractional_resample)
     mix = (["downmix"] if downmix else []) + [f"{k}={_gain_text(v)}" for k, v in (("scale", scale), ("scaleLeft", scale_left), ("scaleRight", scale_right)) if v is not None]
     mix += (["protect"] if protect else []) + (["copyright"] if copyright else []) + ([] if original else ["original=0"]) + (["privateBit"] if private_bit else []) + ([f"emphasis={int(emphasis)}"] if emphasis else [])
+    mix += ["infoTag"] if info_tag else []
     f = _TABLE_DIR / f"t_{channels}_{samplerate}_{kbps}{'_joint' if joint else ''}{'_resv' if reservoir else ''}{'_frac' if frac else ''}{''.join('_' + m.replace('=', '') for m in mix)}.bin"
     if not f.exists() or not blob_is_current(f.read_bytes()):      # a cached blob made by another version of its generator is stale
         _TABLE_DIR.mkdir(exist_ok=True)
@@ -228,7 +244,7 @@ class Mp3Encoder:
 
     def __init__(self, channels: int = 1, samplerate: int = 44100, kbps: int = 128, device: int = -1, lib=None, joint: bool = False, reservoir: bool = False,
                  fractional_resample: bool = False, downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False,
-                 copyright: bool = False, original: bool = True, private_bit: bool = False, emphasis: int = 0):
+                 copyright: bool = False, original: bool = True, private_bit: bool = False, emphasis: int = 0, info_tag: bool = False):
         """``joint`` (extension, not in the reference's wrapper): encode two channels in the reference's joint-stereo mode --
         per frame mid/side or left/right, as its encoder core decides when asked for MPEGMode.JOINT_STEREO.
         ``reservoir`` (extension): encode with the bit reservoir in use (the reference's wrapper disables it, index.js:108); the frames
@@ -243,12 +259,15 @@ class Mp3Encoder:
         gains, applied in its order and with its roundings (include/lamejs_hip.h, "Input gains and downmix").
         ``protect`` (extension): CRC-protected frames, the reference core's ``gfp.error_protection`` (LAME's ``-p``) -- the same frame sizes,
         two more bytes of side information and so 16 bits less main data per frame.  ``copyright``, ``original``, ``private_bit``,
-        ``emphasis`` (0, 1 or 3; 2 is reserved): the header bits of those names.  A value outside these raises ``ValueError``."""
+        ``emphasis`` (0, 1 or 3; 2 is reserved): the header bits of those names.  A value outside these raises ``ValueError``.
+        ``info_tag`` (extension): the stream is a file -- its first call returns the placeholder of an Info/LAME tag frame in front of the audio
+        (which is byte for byte the stream without the option), ``stream_info()`` reports the totals, and after ``flush()``
+        ``info_tag_frame()`` returns the finished frame to be written over the placeholder at offset 0 (include/lamejs_hip.h, "Info tag")."""
         self._lib = lib or load_library()
         self.channels, self.samplerate, self.kbps = int(channels), int(samplerate), int(kbps)
         self._resv = bool(reservoir)
         blob = tables_blob(self.channels, self.samplerate, self.kbps, joint, reservoir, fractional_resample, downmix, scale, scale_left, scale_right,
-                           protect, copyright, original, private_bit, emphasis)
+                           protect, copyright, original, private_bit, emphasis, info_tag)
         cfg = _Config(self.channels, self.samplerate, self.kbps, device)
         h = ctypes.c_void_p()
         buf = ctypes.create_string_buffer(blob, len(blob))
@@ -256,6 +275,22 @@ class Mp3Encoder:
         if rc != 0:
             raise LhipError(f"lhip_create failed ({rc}): {self._lib.lhip_last_error().decode()}")
         self._h = h
+
+    def stream_info(self) -> dict:
+        """``info_tag`` streams: frames, audio bytes, music CRC, delay, padding (-1 before ``flush()``) and the tag frame's size."""
+        si = StreamInfo()
+        rc = self._lib.lhip_stream_info(self._h, ctypes.byref(si))
+        if rc != 0:
+            raise LhipError(f"lhip_stream_info failed ({rc}): {self._lib.lhip_last_error().decode()}")
+        return {"frames": si.frames, "audio_bytes": si.audio_bytes, "music_crc": si.music_crc, "delay": si.delay, "padding": si.padding, "tag_bytes": si.tag_bytes}
+
+    def info_tag_frame(self) -> bytes:
+        """``info_tag`` streams, after ``flush()``: the finished Info/LAME tag frame -- write it over the placeholder at offset 0 of the file."""
+        out = np.empty(2880, dtype=np.uint8)
+        n = self._lib.lhip_info_tag(self._h, out.ctypes.data, len(out))
+        if n < 0:
+            raise LhipError(f"lhip_info_tag failed ({n}): {self._lib.lhip_last_error().decode()}")
+        return out[:n].tobytes()
 
     def call_limit(self) -> int:
         """``fractional_resample`` streams: the ``encodeBuffer`` length that is accepted whatever calls came before (0: any length goes)."""

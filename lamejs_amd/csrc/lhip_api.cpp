@@ -17,6 +17,7 @@
 #include "k_quant_tail.h"      // how a launch of the persistent quantization kernel ends (the one-lane simulation has no workgroups: it runs kb_quant)
 #endif
 #include "k_bits.h"
+#include "k_crc.h"
 
 #include <string>
 #include <vector>
@@ -39,6 +40,7 @@ using namespace lhip;
 #ifndef LHIP_HOSTSIM
 #include "lhip_kernels.h"
 #endif
+#include "lhip_infotag.h"
 #include "lhip_tables.h"
 #include "lhip_context.h"
 #include "lhip_batch.h"
@@ -90,6 +92,44 @@ __global__ void g_math(int op, const double* in, double* out, size_t n, PowBase 
     out[i] = r;
 }
 #endif
+
+// { infoTag }: the placeholder of the tag frame goes out in front of the audio of the stream's first call
+static size_t tag_pending_bytes(const lhip_stream* s) { return (s->tag && !s->tag->placed) ? (size_t)s->ts->tag.size : 0; }
+
+// { infoTag }: the first call of such a stream (an encode call with samples, or the flush: ns == nullptr) returns the tag frame's placeholder in front of
+// its audio -- LAME's contract.  The host writes it where the caller's buffer begins and the call proper sees the buffer behind it; the bytes count
+// as written, and the stream as served, only when the call succeeded (a failed call consumes nothing).  inner(out, cap, written) -> code.
+template <class Fn>
+static int tagged_call(lhip_stream* const* streams, size_t n, const size_t* ns, uint8_t* const* out, const size_t* cap, int64_t* written, bool dev_io, Fn&& inner) {
+    bool any = false;
+    if (streams && out && cap)
+        for (size_t i = 0; i < n && !any; i++) any = streams[i] && streams[i]->magic == 0x4c484950 && streams[i]->tag && !streams[i]->tag->placed && (!ns || ns[i] > 0);
+    if (!any) return inner(out, cap, written);
+    std::vector<uint8_t*> o(out, out + n); std::vector<size_t> c(cap, cap + n); std::vector<size_t> pre(n, 0); std::vector<int64_t> w(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        lhip_stream* s = streams[i];
+        if (!(s && s->magic == 0x4c484950 && s->tag && !s->tag->placed && (!ns || ns[i] > 0))) continue;
+        for (size_t k = 0; k < i; k++) if (streams[k] == s) { s = nullptr; break; }      // (a handle twice in one batch: the call proper reports it)
+        if (!s) continue;
+        pre[i] = (size_t)s->ts->tag.size;
+        if (!out[i] || cap[i] < pre[i]) { set_err("output buffer too small"); for (size_t k = 0; k < n; k++) if (written) written[k] = LHIP_ERR_BUFFER_TOO_SMALL; return LHIP_ERR_BUFFER_TOO_SMALL; }
+        std::vector<uint8_t> ph(pre[i]);
+        tag_placeholder(s->ts->T, s->ts->tag, ph.data());
+        if (!dev_io) memcpy(out[i], ph.data(), pre[i]);
+        else {
+            Context* ctx = s->ctx;
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            if (!rt::set_device(ctx->device) || !rt::h2d(out[i], ph.data(), pre[i], ctx->stream)) return LHIP_ERR_INTERNAL;
+        }
+        o[i] += pre[i]; c[i] -= pre[i];
+    }
+    const int rc = inner(o.data(), c.data(), w.data());
+    for (size_t i = 0; i < n; i++) {
+        if (w[i] >= 0 && pre[i]) { w[i] += (int64_t)pre[i]; streams[i]->tag->placed = true; }
+        if (written) written[i] = w[i];
+    }
+    return rc;
+}
 
 // ===========================================================================================
 // C ABI
@@ -179,6 +219,7 @@ int lhip_create(const lhip_config* cfg, const void* tables, size_t tables_bytes,
     }
     std::unique_ptr<lhip_stream> s(new lhip_stream());
     s->ctx = ctx; s->ts = ts;
+    if (ts->tag.on) s->tag.reset(new TagTotals());
     s->slot_lag = ts->T.frac_SpF;
     // initial carried state (PsyModel.js:2566-2596 psymodel_init, Lame.js:168-171 lame_init_old)
     std::unique_ptr<StreamState> h(new StreamState());
@@ -220,7 +261,7 @@ void lhip_destroy(lhip_stream* s) {
 size_t lhip_max_output_bytes(const lhip_stream* s, size_t nsamples) {
     if (!s || s->magic != 0x4c484950) return 0;
     const size_t frame = 576 * (size_t)s->ts->T.mode_gr;
-    return (nsamples / frame + 3 + (FRAME / frame)) * (size_t)(s->ts->base_frame_bytes + 1) + (s->ts->T.disable_reservoir ? 0 : 4096);      // reservoir: slack for the per-launch bound
+    return (nsamples / frame + 3 + (FRAME / frame)) * (size_t)(s->ts->base_frame_bytes + 1) + (s->ts->T.disable_reservoir ? 0 : 4096) + tag_pending_bytes(s);      // reservoir: slack for the per-launch bound
 }
 
 int64_t lhip_encode_output_bytes(const lhip_stream* s, size_t nsamples) {
@@ -228,7 +269,7 @@ int64_t lhip_encode_output_bytes(const lhip_stream* s, size_t nsamples) {
     if (!s->ts->T.disable_reservoir) return (int64_t)lhip_max_output_bytes(s, nsamples);      // data-dependent: only a bound exists
     const int F = call_frames(s, nsamples);
     if (F < 0) { set_err(s->rs_flushed ? std::string("fractionalResample: the stream has been flushed") : frac_refusal(s->ts->T, nsamples)); return LHIP_ERR_INTERNAL; }      // the call would be refused
-    return batch_bytes(*s->ts, s->slot_lag, F);
+    return batch_bytes(*s->ts, s->slot_lag, F) + (nsamples > 0 ? (int64_t)tag_pending_bytes(s) : 0);
 }
 
 int lhip_output_bytes_is_exact(const lhip_stream* s) {
@@ -294,13 +335,16 @@ int64_t lhip_encode_pcm(lhip_stream* s, int format, const void* left, const void
     if (nsamples == 0) return 0;
     if (!left) { set_err("null input"); return LHIP_ERR_INTERNAL; }
     if (!host_samples_ok(0, s->ts->T.channels_in, s->ts->T.pcm_limit, format, left, right, nsamples)) return LHIP_ERR_INTERNAL;
-    {
+    int64_t w = 0;
+    const int rc = tagged_call(&s, 1, &nsamples, &out, &out_cap, &w, false, [&](uint8_t* const* o, const size_t* c, int64_t* wr) -> int {
         static const bool no_chunk = []() { const char* e = getenv("LAMEJS_HIP_NO_HOST_CHUNKS"); return e && e[0] == '1'; }();
         const Tables& T = s->ts->T;
-        if (!no_chunk && T.disable_reservoir && !T.rs_frac && nsamples > (size_t)2 * host_chunk_schedule().first * 576 * T.mode_gr * T.rs_ratio) return encode_host_chunked(s, format, left, right, nsamples, out, out_cap);
-    }
-    int64_t w = 0;
-    const int rc = encode_many(&s, 1, format, &left, &right, &nsamples, &out, &out_cap, &w, false, true);
+        if (!no_chunk && T.disable_reservoir && !T.rs_frac && nsamples > (size_t)2 * host_chunk_schedule().first * 576 * T.mode_gr * T.rs_ratio) {
+            wr[0] = encode_host_chunked(s, format, left, right, nsamples, o[0], c[0]);
+            return wr[0] < 0 ? (int)wr[0] : 0;
+        }
+        return encode_many(&s, 1, format, &left, &right, &nsamples, o, c, wr, false, true);
+    });
     return rc < 0 ? rc : w;
 }
 int64_t lhip_encode(lhip_stream* s, const int16_t* left, const int16_t* right, size_t nsamples, uint8_t* out, size_t out_cap) {
@@ -316,14 +360,24 @@ int64_t lhip_flush(lhip_stream* s, uint8_t* out, size_t out_cap) {
     const void* l = zeros.data();
     const void* r = zeros.data();
     int64_t w = 0;
-    const int rc = encode_many(&s, 1, LHIP_PCM_S16, &l, &r, &z, &out, &out_cap, &w, false, true, true);
+    const double end_padding = flush_end_padding(s);
+    const int rc = tagged_call(&s, 1, nullptr, &out, &out_cap, &w, false, [&](uint8_t* const* o, const size_t* c, int64_t* wr) -> int {
+        return encode_many(&s, 1, LHIP_PCM_S16, &l, &r, &z, o, c, wr, false, true, true); });
     if (rc < 0) return rc;                 // nothing was consumed (e.g. -1: the call can be repeated with a larger buffer)
     s->mf_samples_to_encode = 0;
+    if (s->tag) { s->tag->padding = end_padding; s->tag->flushed = true; }
     return w;
 }
 
+static int encode_batch_pcm_inner(lhip_stream* const* streams, size_t nstreams, int format, const void* const* left, const void* const* right,
+                                  const size_t* nsamples, uint8_t* const* out, const size_t* out_cap, int64_t* written);
 int lhip_encode_batch_pcm(lhip_stream* const* streams, size_t nstreams, int format, const void* const* left, const void* const* right,
                           const size_t* nsamples, uint8_t* const* out, const size_t* out_cap, int64_t* written) {
+    return tagged_call(streams, nstreams, nsamples, out, out_cap, written, false, [&](uint8_t* const* o, const size_t* c, int64_t* wr) -> int {
+        return encode_batch_pcm_inner(streams, nstreams, format, left, right, nsamples, o, c, wr); });
+}
+static int encode_batch_pcm_inner(lhip_stream* const* streams, size_t nstreams, int format, const void* const* left, const void* const* right,
+                                  const size_t* nsamples, uint8_t* const* out, const size_t* out_cap, int64_t* written) {
     if (!fmt_ok(format)) { set_err("unknown sample format"); return LHIP_ERR_INTERNAL; }
     if ((format & LHIP_PCM_F32) && streams && left && nsamples)       // every stream's samples are looked at before any stream consumes anything
         for (size_t i = 0; i < nstreams; i++)
@@ -374,19 +428,26 @@ int lhip_flush_batch(lhip_stream* const* streams, size_t nstreams, uint8_t* cons
         zs[i].assign(ns[i] ? ns[i] : 1, 0);
         l[i] = zs[i].data();
     }
-    const int rc = encode_many(streams, nstreams, LHIP_PCM_S16, l.data(), l.data(), ns.data(), out, out_cap, written, false, true, true);
-    if (rc >= 0) for (size_t i = 0; i < nstreams; i++) streams[i]->mf_samples_to_encode = 0;
+    std::vector<double> end_padding(nstreams);
+    for (size_t i = 0; i < nstreams; i++) end_padding[i] = flush_end_padding(streams[i]);
+    const int rc = tagged_call(streams, nstreams, ns.data(), out, out_cap, written, false, [&](uint8_t* const* o, const size_t* c, int64_t* wr) -> int {
+        return encode_many(streams, nstreams, LHIP_PCM_S16, l.data(), l.data(), ns.data(), o, c, wr, false, true, true); });
+    if (rc >= 0) for (size_t i = 0; i < nstreams; i++) {
+        streams[i]->mf_samples_to_encode = 0;
+        if (streams[i]->tag && ns[i] > 0) { streams[i]->tag->padding = end_padding[i]; streams[i]->tag->flushed = true; }
+    }
     return rc;
 }
 
 int lhip_encode_batch_device(lhip_stream* const* streams, size_t nstreams, const int16_t* const* d_left, const int16_t* const* d_right,
                              const size_t* nsamples, uint8_t* const* d_out, const size_t* out_cap, int64_t* written, int sync) {
-    return encode_many(streams, nstreams, LHIP_PCM_S16, (const void* const*)d_left, (const void* const*)d_right, nsamples, d_out, out_cap, written, true, sync != 0);
+    return lhip_encode_batch_device_pcm(streams, nstreams, LHIP_PCM_S16, (const void* const*)d_left, (const void* const*)d_right, nsamples, d_out, out_cap, written, sync);
 }
 int lhip_encode_batch_device_pcm(lhip_stream* const* streams, size_t nstreams, int format, const void* const* d_left, const void* const* d_right,
                                  const size_t* nsamples, uint8_t* const* d_out, const size_t* out_cap, int64_t* written, int sync) {
     if (!fmt_ok(format)) { set_err("unknown sample format"); return LHIP_ERR_INTERNAL; }
-    return encode_many(streams, nstreams, format, d_left, d_right, nsamples, d_out, out_cap, written, true, sync != 0);
+    return tagged_call(streams, nstreams, nsamples, d_out, out_cap, written, true, [&](uint8_t* const* o, const size_t* c, int64_t* wr) -> int {
+        return encode_many(streams, nstreams, format, d_left, d_right, nsamples, o, c, wr, true, sync != 0); });
 }
 int64_t lhip_last_batch_rejected_samples(void) {
     if (g_rej_pending) {                       // the count is on the device: wait for the batch and fetch it
@@ -456,6 +517,7 @@ int lhip_state_set(lhip_stream* s, const void* buf, size_t n) {
     if (!rt::set_device(ctx->device)) return LHIP_ERR_INTERNAL;
     if (!rt::set_device(ctx->device) || !rt::h2d(s->d_state, (const uint8_t*)buf + sizeof h, sizeof(StreamState), ctx->stream) || !rt::sync(ctx->stream)) return LHIP_ERR_INTERNAL;
     s->mf_size = h.mf_size; s->mf_samples_to_encode = h.mf_samples_to_encode; s->slot_lag = h.slot_lag; s->frame_num = h.frame_num; s->rs_n_in = h.rs_n_in;
+    if (s->tag) s->tag->moved = true;          // (state blobs do not carry the tag's totals)
     return 0;
 }
 size_t lhip_seek_tail_samples(const lhip_stream* s) {
@@ -498,6 +560,7 @@ int lhip_seek(lhip_stream* s, int64_t sample_pos, const int16_t* tail_left, cons
     if (!rt::set_device(ctx->device) || !rt::h2d((uint8_t*)s->d_state + offsetof(StreamState, pcm_tail), t.data(), sizeof(float) * 2 * MF_NEEDED, ctx->stream) || !rt::sync(ctx->stream)) return LHIP_ERR_INTERNAL;
     const int64_t k = sample_pos / frame;                     // the stream has emitted k - 1 frames
     s->frame_num = k - 1;
+    if (s->tag) s->tag->moved = true;
     s->rs_n_in = sample_pos;
     s->mf_size = ntail;
     s->mf_samples_to_encode = 576 + 1152 + frame;
@@ -619,6 +682,75 @@ int64_t lhip_debug_read(int what, void* dst, size_t cap) {
     if (n > cap) n = cap;
     if (!rt::d2h(dst, src, n, ctx->stream) || !rt::sync(ctx->stream)) return LHIP_ERR_INTERNAL;
     return (int64_t)n;
+}
+
+// ---- the Info tag (extension { infoTag }; lhip_infotag.h) ----
+int lhip_stream_info(const lhip_stream* s, lhip_stream_info_t* info) {
+    if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    if (!info) { set_err("lhip_stream_info: null argument"); return LHIP_ERR_INTERNAL; }
+    if (!s->tag) { set_err("lhip_stream_info: the stream was not created with the infoTag option (its totals are not kept)"); return LHIP_ERR_INTERNAL; }
+    const TagTotals& v = *s->tag;
+    info->frames = v.frames; info->audio_bytes = v.bytes; info->music_crc = v.crc & 0xffff; info->delay = s->ts->tag.delay;
+    info->padding = v.padding < 0 ? -1 : (int32_t)v.padding; info->tag_bytes = s->ts->tag.size;
+    return 0;
+}
+int64_t lhip_info_tag(lhip_stream* s, uint8_t* out, size_t cap) {
+    if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    if (!s->tag) { set_err("lhip_info_tag: the stream was not created with the infoTag option"); return LHIP_ERR_INTERNAL; }
+    if (s->tag->moved) { set_err("lhip_info_tag: the stream was moved with lhip_seek or lhip_state_set; state blobs do not carry the tag's totals (combining the tags of shards is not supported)"); return LHIP_ERR_INTERNAL; }
+    if (!s->tag->flushed) { set_err("lhip_info_tag: the stream has not been flushed (the tag reports the totals and the end padding of the complete stream)"); return LHIP_ERR_INTERNAL; }
+    const size_t n = (size_t)s->ts->tag.size;
+    if (!out || cap < n) { set_err("output buffer too small"); return LHIP_ERR_BUFFER_TOO_SMALL; }
+    tag_write(s->ts->T, s->ts->tag, *s->tag, out);
+    return (int64_t)n;
+}
+// Test hooks.  lhip_debug_crc_span: the bytes one workgroup of the CRC kernel covers.  lhip_debug_crc16: the kernel (in the simulations: its body) over a
+// caller's buffer, placed `misalign` bytes past a 16-byte boundary -- always the device path, whatever n is.  lhip_debug_info_toc: the seek-table
+// bookkeeping alone, fed ncalls batches of frames[i] frames of `kbps`.
+size_t lhip_debug_crc_span(void) { return (size_t)CRC_SPAN_BYTES; }
+int lhip_debug_crc16(const void* bytes, size_t n, size_t misalign, uint32_t* crc) {
+    if ((!bytes && n) || !crc || misalign > 15 || n > (size_t)1 << 40) { set_err("lhip_debug_crc16: bad argument"); return LHIP_ERR_INTERNAL; }
+    if (rt::device_count() <= 0) { set_err("no HIP device available (this library has no CPU fallback)"); return LHIP_ERR_INTERNAL; }
+    CrcDesc d;
+    d.n = (int64_t)n; d.n_dev = nullptr; d.part0 = 0; d.nparts = (int32_t)((n + CRC_SPAN_BYTES - 1) / CRC_SPAN_BYTES);
+    uint8_t* buf = (uint8_t*)rt::dmalloc(n + 32);
+    uint8_t* aux = (uint8_t*)rt::dmalloc(sizeof(CrcDesc) + 16 + (size_t)d.nparts * 4);      // [descriptor | result | span remainders]
+    bool ok = buf && aux;
+    if (ok) {
+        d.base = buf + ((16 - ((uintptr_t)buf & 15)) & 15) + misalign;
+        CrcDesc* dD = (CrcDesc*)aux; uint32_t* dOut = (uint32_t*)(aux + sizeof(CrcDesc)); uint32_t* dPart = dOut + 4;
+        ok = rt::h2d((void*)d.base, bytes, n, nullptr) && rt::h2d(dD, &d, sizeof d, nullptr) && rt::sync(nullptr);
+#ifndef LHIP_HOSTSIM
+        if (ok) {
+            if (d.nparts > 0) hipLaunchKernelGGL(g_out_crc, dim3(d.nparts), dim3(64), 0, 0, (const CrcDesc*)dD, 1, dPart);
+            hipLaunchKernelGGL(g_out_crc_fold, dim3(1), dim3(64), 0, 0, (const CrcDesc*)dD, (const uint32_t*)dPart, dOut);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { set_err(std::string("g_out_crc: ") + hipGetErrorString(e)); ok = false; }
+        }
+#else
+        if (ok) {
+#ifdef LHIP_WAVESIM
+            for (int b = 0; b < d.nparts; b++) wsim::run([&](int lane_) { kb_out_crc(dD, crc_find_stream(dD, 1, b), b, lane_, dPart); });
+            wsim::run([&](int lane_) { kb_crc_fold(dD, 0, lane_, dPart, dOut); });
+#else
+            for (int b = 0; b < d.nparts; b++) kb_out_crc(dD, crc_find_stream(dD, 1, b), b, 0, dPart);
+            kb_crc_fold(dD, 0, 0, dPart, dOut);
+#endif
+        }
+#endif
+        uint32_t r = 0;
+        ok = ok && rt::d2h(&r, dOut, 4, nullptr) && rt::sync(nullptr);
+        *crc = r & 0xffff;
+    } else set_err("hipMalloc failed");
+    rt::dfree(buf); rt::dfree(aux);
+    return ok ? 0 : LHIP_ERR_INTERNAL;
+}
+int lhip_debug_info_toc(const int64_t* frames, size_t ncalls, int kbps, uint8_t* toc) {
+    if ((!frames && ncalls) || !toc || kbps <= 0) { set_err("lhip_debug_info_toc: bad argument"); return LHIP_ERR_INTERNAL; }
+    std::unique_ptr<TagTotals> v(new TagTotals());
+    for (size_t i = 0; i < ncalls; i++) { if (frames[i] < 0) { set_err("lhip_debug_info_toc: bad argument"); return LHIP_ERR_INTERNAL; } tag_toc_add(*v, frames[i], kbps); }
+    tag_toc(*v, toc);
+    return v->pos;
 }
 
 int lhip_kernel_timing(int enable) {

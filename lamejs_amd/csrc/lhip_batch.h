@@ -121,6 +121,11 @@ struct BatchPlan {
     std::vector<int64_t> out_rel;                  // a stream's output offset inside the output area (sd.out_off becomes the absolute address in stage_inputs)
     CallLayout L; Workspace W;
     const StreamDesc* dSD = nullptr; const StreamIO* dIO = nullptr;
+    // { infoTag } streams: where this call's music CRCs come from -- 0: no such stream, 1: the host's table CRC over the pinned mirror (small calls),
+    // 2: g_out_crc over the bytes in HBM (crc_parts workgroups; results to crc_dst on the device, fetched into crc unless the caller keeps a log)
+    int crc_mode = 0, crc_parts = 0;
+    uint32_t* crc_dst = nullptr;
+    std::vector<uint32_t> crc;                     // per stream
 };
 
 static bool plan_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, BatchPlan& P) {
@@ -204,6 +209,25 @@ static bool bind_workspace(Context* ctx, BatchPlan& P) {
         W.seed_flag = (int32_t*)(smb + L.sm_sf); W.reval = (int32_t*)(smb + L.sm_rv);
     } else if (!P.dev_io && !(ws.in16.ensure(P.in_bytes + 64) && ws.out8.ensure((size_t)P.out_total + 64))) return false;
     if (P.small) P.paths |= LHIP_PATH_SMALL_CALL;
+    if (P.ts->tag.on) { P.crc_mode = P.small ? 1 : 2; P.crc.assign((size_t)S, 0u); }
+    return true;
+}
+// { infoTag } streams whose bytes stay on the device: one descriptor per stream for g_out_crc (the byte count of a bit-reservoir stream is read on the device)
+static bool stage_crc(Context* ctx, const std::vector<Job>& jobs, BatchPlan& P, uint32_t* crc_log) {
+    WorkSet& ws = ctx->ws; const int S = P.S;
+    std::vector<CrcDesc> cd((size_t)S);
+    int64_t parts = 0;
+    for (int i = 0; i < S; i++) {
+        CrcDesc& d = cd[i];
+        d.base = P.io[i].out; d.n = jobs[i].bytes; d.n_dev = P.resv ? P.W.out_bytes + i : nullptr;      // (jobs[i].bytes: exact, or the reservoir's upper bound)
+        d.part0 = (int32_t)parts; d.nparts = (int32_t)((jobs[i].bytes + CRC_SPAN_BYTES - 1) / CRC_SPAN_BYTES);
+        parts += d.nparts;
+    }
+    if (parts > 0x7fffffff) { set_err("too many output bytes in one call for the Info tag's CRC"); return false; }
+    P.crc_parts = (int)parts;
+    if (!ws.crc_desc.ensure((size_t)S * sizeof(CrcDesc)) || !ws.crc_part.ensure((size_t)parts * 4 + 64) || !ws.crc_out.ensure((size_t)S * 4 + 64)) return false;
+    if (!rt::h2d(ws.crc_desc.p, cd.data(), (size_t)S * sizeof(CrcDesc), ctx->stream)) return false;
+    P.crc_dst = crc_log ? crc_log : (uint32_t*)ws.crc_out.p;
     return true;
 }
 static bool stage_inputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P) {
@@ -284,7 +308,7 @@ static bool stage_inputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P) {
     W.io = P.dIO;
     return true;
 }
-static bool fetch_outputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P, bool want_sync, int32_t* fx_dst, bool fetch_fx, int32_t (&fx)[3]) {
+static bool fetch_outputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P, bool want_sync, int32_t* fx_dst, bool fetch_fx, int32_t (&fx)[3], bool fetch_crc) {
     WorkSet& ws = ctx->ws; void* st = ctx->stream; const Workspace& W = P.W; const CallLayout& L = P.L;
     const int S = P.S, nfr = P.nfr; const bool small = P.small, dev_io = P.dev_io, resv = P.resv;
     const uint8_t* const smb = (const uint8_t*)ws.small.p;
@@ -300,6 +324,7 @@ static bool fetch_outputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P, bo
         memcpy(fx, po + L.sm_nfl + FX_STATS_OFF, sizeof fx);
         if (resv) for (int i = 0; i < S; i++) jobs[i].bytes = ((const int32_t*)(po + L.sm_ob))[i];
         for (int i = 0; i < S; i++) if (jobs[i].bytes > 0) memcpy(jobs[i].out, po + L.sm_out + P.out_rel[i], (size_t)jobs[i].bytes);
+        if (P.crc_mode == 1) for (int i = 0; i < S; i++) P.crc[i] = crc16r_host(po + L.sm_out + P.out_rel[i], (size_t)jobs[i].bytes);      // { infoTag }: the bytes are here anyway
     } else {
         if (fetch_fx && !rt::d2h(fx, (const int32_t*)ws.nflagged.p + FX_STATS_OFF / 4, sizeof fx, st)) return false;
         std::vector<int32_t> ob;
@@ -308,11 +333,12 @@ static bool fetch_outputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P, bo
             if (!rt::d2h(ob.data(), ws.out_bytes.p, (size_t)S * 4, st) || !rt::sync(st)) return false;
             for (int i = 0; i < S; i++) jobs[i].bytes = ob[i];
         }
+        if (fetch_crc && !rt::d2h(P.crc.data(), P.crc_dst, (size_t)S * 4, st)) return false;      // { infoTag }: rides with the copies back; a device-pointer call waits for it
         if (!dev_io) {
             for (int i = 0; i < S; i++)
                 if (jobs[i].bytes > 0 && !rt::d2h(jobs[i].out, P.io[i].out, (size_t)jobs[i].bytes, st)) return false;
             if (!rt::sync(st)) return false;
-        } else if (want_sync) {
+        } else if (want_sync || fetch_crc) {
             if (!rt::sync(st)) return false;
         }
     }
@@ -355,7 +381,9 @@ static void advance_streams(std::vector<Job>& jobs, const Tables& T) {
 
 // fx_dst (device, optional): where this batch's repair verdict (three words: repaired frames, iterations, "did not converge") is copied on the launch
 // stream while ctx->mu is still held -- the chunked host path logs one per unit, and another thread's batch on the same device must not get in between
-static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool want_sync, int32_t* fx_dst = nullptr) {
+// crc_log (device, optional; { infoTag } streams): where this batch's music CRCs (one word per stream) are left instead of being fetched -- the caller reads its log once
+// and does the streams' tag accounting itself (tag_account)
+static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool want_sync, int32_t* fx_dst = nullptr, uint32_t* crc_log = nullptr) {
     if (jobs.empty()) return true;
 #ifdef LHIP_PHASE_PROF
     auto cp_t_ = std::chrono::steady_clock::now();
@@ -367,6 +395,7 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     if (!plan_batch(ctx, jobs, dev_io, P) || !bind_workspace(ctx, P)) return false;
     CALL_STAMP(0);                                  // plan + workspace
     if (!stage_inputs(ctx, jobs, P)) return false;
+    if (P.crc_mode == 2 && !stage_crc(ctx, jobs, P, crc_log)) return false;
     CALL_STAMP(1);                                  // input copies, descriptors, counters zeroed: enqueued
 
     g_rejected = 0; g_rej_pending = nullptr;
@@ -376,9 +405,10 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     // when somebody asks (lhip_last_batch_stats)
     int32_t fx[3] = {0, 0, 0};
     const bool fetch_fx = P.nfr > 0 && (!dev_io || want_sync || g_kt_on_());
-    if (!fetch_outputs(ctx, jobs, P, want_sync, fx_dst, fetch_fx, fx) || !collect_kernel_times(ctx->stream)) return false;
+    if (!fetch_outputs(ctx, jobs, P, want_sync, fx_dst, fetch_fx, fx, P.crc_mode == 2 && !crc_log) || !collect_kernel_times(ctx->stream)) return false;
     CALL_STAMP(3);                                  // output copies + synchronisation
     advance_streams(jobs, P.ts->T);
+    if (P.crc_mode && !crc_log) for (int i = 0; i < P.S; i++) tag_account(*jobs[i].s->tag, jobs[i].F, jobs[i].bytes, P.crc[i], P.ts->T.brate);
     if (!collect_repair_stats(ctx, P, fetch_fx, fx)) return false;
     g_stat_frames = P.nfr; g_stat_repaired = P.repaired; g_stat_iters = P.iters; g_last_paths = P.paths;
     WorkSet& ws = ctx->ws;

@@ -40,6 +40,7 @@ struct PinBuf {
 struct WorkSet {
     DevBuf pcm, peaks, loud, eb_l, mask_idx, eb_s, ecb_s, att_raw, uselong, ul_tmp, last_attack, tent, prev_short, blocktype,
         ath_adjust, ath_limit, E, sb, xr, side, l3, seed, seed_flag, nflagged, slow_list, frame_bytes, desc, in16, rejected, out8, prof, fht, hpf, tot_ener, reval, att_clean, nb1, nb2, fr, out_bytes, vdig, small;
+    DevBuf crc_desc, crc_part, crc_out;     // { infoTag } streams only (g_out_crc): per-stream descriptors, span remainders, results
     PinBuf pin_in, pin_out;     // small host-buffer calls (run_batch): everything that travels in / out, staged once in pinned memory
     // last batch (for debug taps)
     Workspace lastW; int lastC = 0, lastCp = 0; bool have_last = false;
@@ -62,6 +63,7 @@ struct Context {
     // large host-buffer calls (the drop-in's encodeBuffer with a long Int16Array): chunks of the call are copied in on this stream
     // while the chunk before is being encoded and the one before that is copied out (encode_host_chunked)
     void* copy_stream = nullptr; void* ev_in[2] = {nullptr, nullptr}; void* ev_done[2] = {nullptr, nullptr};
+    DevBuf chunk_crc;           // ... and, for { infoTag } streams, the music CRCs of the call's pieces (read back once, after the last unit)
     DevBuf chunk_in, chunk_out, chunk_fx, state_bak;     // staging halves (sized for the largest chunk a call has reached so far), the per-chunk repair verdicts, the stream state a failed call gives back
     std::mutex chunk_mu;        // one chunked call at a time per device (they share the two staging halves); taken BEFORE mu, never inside it
 };
@@ -100,5 +102,6 @@ struct lhip_stream {
     double rs_inbuf_nsamples = 0;  // gfc.in_buffer_nsamples: the largest call so far (fractional after a flush bunch) ...
     int64_t rs_inbuf_len = 0;      // ... and the length of the persistent input buffer allocated for it (Lame.js:1373-1379)
     bool rs_flushed = false;       // flush() has run: the reference's resampler holds NaN from then on, the stream ends there
+    std::unique_ptr<TagTotals> tag;   // { infoTag } streams: what the tag frame will report (lhip_infotag.h); null otherwise
     ~lhip_stream() { rt::dfree(d_state); magic = 0; }
 };

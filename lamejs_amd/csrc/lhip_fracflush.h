@@ -1,6 +1,18 @@
 // lhip_fracflush.h -- what flush() feeds: the zeros of an ordinary stream (flush_zeros) and the planned flush of a non-integer-ratio stream.
 // Part of lhip_api.cpp's one translation unit (included there, in the order the definitions need).
 #pragma once
+// gfp.encoder_padding as lame_encode_flush sets it (Lame.js:1393-1412) -- a double where the reference's number can be fractional (16 / r for r = 3);
+// -1 for a stream that has nothing to flush
+static double flush_end_padding(const lhip_stream* s) {
+    if (s->mf_samples_to_encode < 1) return -1;
+    const Tables& T = s->ts->T;
+    const int frame = 576 * T.mode_gr;
+    double samples_to_encode = s->mf_samples_to_encode - 1152;
+    if (T.in_samplerate != T.out_samplerate) samples_to_encode += 16. * T.out_samplerate / T.in_samplerate;
+    double end_padding = frame - fmod(samples_to_encode, (double)frame);
+    if (end_padding < 576) end_padding += frame;
+    return end_padding;
+}
 static size_t flush_zeros(lhip_stream* s) {
     // Lame.js:1381-1443: the flush loop feeds bunches of at most 1152 zeros (fill_buffer takes them one frame at a
     // time) until `frames_left` bunches have each completed at least one frame; the total number of zeros is what

@@ -59,6 +59,13 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
     const int f32 = format & LHIP_PCM_F32;
     const size_t bps = fmt_bps(f32);
     const bool il = (format & LHIP_PCM_INTERLEAVED) && C == 2;
+    // { infoTag } streams: every piece's music CRC stays on the device in the call's log (run_batch: crc_log) and the totals of the streams are brought up to date
+    // once, after the last unit -- a failed call has then changed none of them
+    const bool tagged = strs[0]->ts->tag.on != 0;
+    struct TagRec { int si, F; int64_t bytes; };
+    std::vector<TagRec> tag_recs;
+    size_t npieces = 0;
+    for (const auto& u : units) npieces += u.size();
     // what a failed call must give back: the host-side counters and the device-side state record of every stream (a call that fails in unit
     // k > 0 would otherwise leave streams k units further on with `out` half written -- "a failed call consumes nothing" has to hold here too)
     struct Snap { int mf, ste, lag; int64_t fn, rs; };
@@ -73,7 +80,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
             for (int i = 0; i < 4; i++) if (!rt::event_create(&e[i])) return LHIP_ERR_INTERNAL;
             ctx->ev_in[0] = e[0]; ctx->ev_in[1] = e[1]; ctx->ev_done[0] = e[2]; ctx->ev_done[1] = e[3]; ctx->copy_stream = cs;
         }
-        if (!ctx->chunk_in.ensure(2 * C * stride * bps + 64) || !ctx->chunk_out.ensure(2 * out_chunk) || !ctx->chunk_fx.ensure(units.size() * 16 + 16) ||
+        if (!ctx->chunk_in.ensure(2 * C * stride * bps + 64) || !ctx->chunk_out.ensure(2 * out_chunk) || !ctx->chunk_fx.ensure(units.size() * 16 + 16) || (tagged && !ctx->chunk_crc.ensure(npieces * 4 + 16)) ||
             !ctx->state_bak.ensure(NS * sizeof(StreamState))) return LHIP_ERR_INTERNAL;
         for (size_t i = 0; i < NS; i++)
             if (!rt::d2d((uint8_t*)ctx->state_bak.p + i * sizeof(StreamState), strs[i]->d_state, sizeof(StreamState), ctx->stream)) return LHIP_ERR_INTERNAL;
@@ -137,7 +144,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
         const double t_b = trace_chunks ? ms_now() : 0.0;
         // (this unit's repair verdict stays on the device until the call ends: run_batch copies it into the call's log -- stream-ordered, under the context's
         //  lock -- and the log is read back once after the last unit)
-        if (!run_batch(ctx, jobs, true, false, (int32_t*)ctx->chunk_fx.p + 4 * k)) { int64_t code = LHIP_ERR_INTERNAL; for (const Job& j : jobs) if (j.written < 0) { code = j.written; break; } return fail(nullptr, code); }
+        if (!run_batch(ctx, jobs, true, false, (int32_t*)ctx->chunk_fx.p + 4 * k, tagged ? (uint32_t*)ctx->chunk_crc.p + tag_recs.size() : nullptr)) { int64_t code = LHIP_ERR_INTERNAL; for (const Job& j : jobs) if (j.written < 0) { code = j.written; break; } return fail(nullptr, code); }
 #ifdef LHIP_HOSTSIM
         // tests: a failure injected after unit k has been consumed (the streams must come back as the call found them)
         if (const char* e = getenv("LHIP_HOSTSIM_FAIL_CHUNK")) if (e[0] && (size_t)atoi(e) == k) return fail("injected failure (LHIP_HOSTSIM_FAIL_CHUNK)");
@@ -152,6 +159,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
             const int si = u[j].si;
             pending.push_back(Pending{dst[si] + total[si], jobs[j].out, jobs[j].written});
             total[si] += jobs[j].written;
+            if (tagged) tag_recs.push_back(TagRec{si, jobs[j].F, jobs[j].written});
         }
         pending_par = par; have_pending = true;
         frames_all += g_stat_frames; paths_all |= g_last_paths;
@@ -168,6 +176,11 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
     }
     g_stat_pending = nullptr;
 #endif
+    if (tagged) {
+        std::vector<uint32_t> crcs(tag_recs.size(), 0u);
+        if (!rt::d2h(crcs.data(), ctx->chunk_crc.p, crcs.size() * 4, ks) || !rt::sync(ks)) return fail(nullptr);
+        for (size_t i = 0; i < tag_recs.size(); i++) tag_account(*strs[tag_recs[i].si]->tag, tag_recs[i].F, tag_recs[i].bytes, crcs[i], T.brate);
+    }
     g_stat_frames = frames_all; g_stat_repaired = repaired_all; g_stat_iters = iters_all;     // lhip_last_batch_stats: the whole call
     g_last_paths = paths_all;                                                                 // lhip_debug_last_paths: every path one of its units took
     for (size_t i = 0; i < NS; i++) written[i] = total[i];

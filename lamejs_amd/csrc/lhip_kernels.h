@@ -261,6 +261,13 @@ __global__ __launch_bounds__(64) void g_resv_flush(Tables T, Workspace W, const 
     __shared__ BitsLds L;
     if (SD[blockIdx.x].flush) kb_resv_flush(T, W, blockIdx.x, threadIdx.x, L, W.io[blockIdx.x].state->rv, W.out_bytes + blockIdx.x);
 }
+// the music CRC of { infoTag } streams (k_crc.h): one wave per span of a stream's bytes, then one wave per stream folds its spans.  Launched only for a
+// batch of such streams, behind the last kernel that writes output bytes.
+__global__ __launch_bounds__(64) void g_out_crc(const CrcDesc* D, int nstreams, uint32_t* partial) {
+    const int s = crc_find_stream(D, nstreams, (int)blockIdx.x);
+    kb_out_crc(D, s, (int)blockIdx.x - D[s].part0, threadIdx.x, partial);
+}
+__global__ __launch_bounds__(64) void g_out_crc_fold(const CrcDesc* D, const uint32_t* partial, uint32_t* out) { kb_crc_fold(D, blockIdx.x, threadIdx.x, partial, out); }
 #ifndef LHIP_FRAME_PIPE
 #define LHIP_FRAME_PIPE 1      /* 0: the Huffman counts of the outer loop on the searching wave itself (A/B builds) */
 #endif
@@ -342,8 +349,8 @@ template <int RESV> __global__ __launch_bounds__(64 * FR_WAVES) void g_frame(QAr
 #endif
 }
 // optional per-kernel timing with HIP events on the launch stream (bench.py roofline accounting)
-enum { KT_LOAD, KT_PREP, KT_PSYA, KT_SCAN, KT_PSYB, KT_POLY, KT_MDCT, KT_QUANT, KT_VALIDATE, KT_REPAIR, KT_BITS, KT_SAVE, KT_COUNT, KT_N };
-static const char* const g_kt_names[KT_N] = {"load", "prep", "psyA", "scan", "psyB", "polyphase", "mdct", "quant", "validate", "repair", "bits", "save", "count_rejected"};
+enum { KT_LOAD, KT_PREP, KT_PSYA, KT_SCAN, KT_PSYB, KT_POLY, KT_MDCT, KT_QUANT, KT_VALIDATE, KT_REPAIR, KT_BITS, KT_SAVE, KT_COUNT, KT_OUT_CRC, KT_N };
+static const char* const g_kt_names[KT_N] = {"load", "prep", "psyA", "scan", "psyB", "polyphase", "mdct", "quant", "validate", "repair", "bits", "save", "count_rejected", "out_crc"};
 // The switch is process-wide (bench.py turns it on for one extra, untimed step); the events of a batch belong to the calling
 // thread (a batch runs entirely inside one run_batch call), the accumulators are shared by all devices and guarded by g_kt_mu.
 static std::atomic<bool> g_kt_on{false};

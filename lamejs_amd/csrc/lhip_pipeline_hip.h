@@ -138,5 +138,11 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     }
     LAUNCH(KT_SAVE, g_save, S, st, T, W, dSD, dIO);
     }
+    // { infoTag } streams whose bytes stay on the device: their music CRC, behind the last writer of output bytes
+    if (P.crc_mode == 2) {
+        P.paths |= LHIP_PATH_OUT_CRC;
+        LAUNCH(KT_OUT_CRC, g_out_crc, P.crc_parts, st, (const CrcDesc*)ws.crc_desc.p, S, (uint32_t*)ws.crc_part.p);
+        LAUNCH(KT_OUT_CRC, g_out_crc_fold, S, st, (const CrcDesc*)ws.crc_desc.p, (const uint32_t*)ws.crc_part.p, P.crc_dst);
+    }
     return true;
 }

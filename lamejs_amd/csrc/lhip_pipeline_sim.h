@@ -21,7 +21,7 @@ static bool collect_kernel_times(void*) { return true; }
 static bool collect_repair_stats(Context*, BatchPlan&, bool, const int32_t*) { return true; }      // (run_pipeline counted them itself)
 // P.paths: the simulations record what they simulate -- the scalar one has no two-waves-per-frame program and no count helpers, the wave
 // simulation always runs the count helpers, and neither has g_fixup's two launch forms (the repair is the host loop below): no FIXUP bit
-static bool run_pipeline(Context*, BatchPlan& P) {
+static bool run_pipeline(Context* ctx, BatchPlan& P) {
     const TableSet& ts = *P.ts; const Tables& T = ts.T; Workspace& W = P.W; const std::vector<StreamDesc>& sd = P.sd;
     const StreamDesc* dSD = P.dSD; const StreamIO* dIO = P.dIO;
     const int S = P.S, C = T.channels_out, ngs = P.ngs, nfs = P.nfs, nfr = P.nfr; const bool resv = P.resv, use_frame = P.use_frame;
@@ -158,6 +158,12 @@ static bool run_pipeline(Context*, BatchPlan& P) {
     for (int b = 0; b < nfs; b++) WAVE_RUN(kb_bits(T, W, dSD, b, lane_, LBi));
     }
     for (int s = 0; s < S; s++) WAVE_RUN(kb_save(T, W, dSD, dIO, s, lane_));
+    }
+    if (P.crc_mode == 2) {         // g_out_crc and g_out_crc_fold, workgroup by workgroup
+        P.paths |= LHIP_PATH_OUT_CRC;
+        const CrcDesc* D = (const CrcDesc*)ctx->ws.crc_desc.p; uint32_t* part = (uint32_t*)ctx->ws.crc_part.p;
+        for (int b = 0; b < P.crc_parts; b++) { const int s = crc_find_stream(D, S, b); WAVE_RUN(kb_out_crc(D, s, b - D[s].part0, lane_, part)); }
+        for (int s = 0; s < S; s++) WAVE_RUN(kb_crc_fold(D, s, lane_, part, P.crc_dst));
     }
     return true;
 }

@@ -15,7 +15,8 @@ struct TableSet {
     void* d_qtabs = nullptr;
     int device = 0;
     int base_frame_bytes = 0;
-    bool bad_option = false;  // build_tables refused an option of the blob -- input gains, frame protection, header flags (lhip_create: -3)
+    bool bad_option = false;  // build_tables refused an option of the blob -- input gains, frame protection, header flags, the Info tag (lhip_create: -3)
+    InfoTagCfg tag;           // { infoTag } (lhip_infotag.h): host-side only, no kernel sees it
     ~TableSet() { rt::dfree(d_blob); rt::dfree(d_extra); rt::dfree(d_qtabs); }
 };
 
@@ -88,6 +89,17 @@ static bool parse_blob(TableSet& ts, const void* blob, size_t nbytes, void* stre
 #define CDO(f, dflt) { const int k_ = named("cfg_d_names", #f); T.f = k_ >= 0 ? cd[k_] : (dflt); }
     CIO(channels_in, T.channels_out); CIO(do_scale, (!(T.scale == 0.0) && !(T.scale == 1.0)) ? 1 : 0); CIO(do_scale_left, 0); CIO(do_scale_right, 0);
     CDO(scale_left, 0.0); CDO(scale_right, 0.0);
+    // the Info tag (extension { infoTag }): entries only a blob built with the option has; they stay on the host (TableSet::tag)
+    {
+        InfoTagCfg& G = ts.tag;
+#define CTAG(f, key) { const int k_ = named("cfg_i_names", key); G.f = k_ >= 0 ? ci[k_] : 0; }
+        CTAG(on, "info_tag"); CTAG(quality, "tag_quality"); CTAG(method, "tag_method"); CTAG(lowpass, "tag_lowpass"); CTAG(flags, "tag_flags");
+        CTAG(misc, "tag_misc"); CTAG(preset, "tag_preset"); CTAG(delay, "tag_delay");
+#undef CTAG
+        const lhtb_entry* tv = find_entry(b, "tag_version");
+        if (G.on && (!tv || tv->dtype != 1 || tv->count != 9)) { set_err("tables blob: entry missing: tag_version"); ok = false; }
+        else if (G.on) for (int i = 0; i < 9; i++) G.version[i] = (uint8_t)((const int32_t*)(b + tv->offset))[i];
+    }
 #undef CIO
 #undef CDO
     optional = false;
@@ -168,6 +180,19 @@ static bool check_envelope(TableSet& ts, const lhip_config& cfg) {
         }
         // the stand-in frames of a non-integer-ratio stream's flush are written by the host without a CRC of their own
         if (T.error_protection && T.rs_frac) { set_err("frame protection cannot be combined with fractionalResample (the flush's stand-in frames carry no pinned CRC)"); ts.bad_option = true; return false; }
+    }
+    // the Info tag (extension { infoTag }): the frame must hold the tag behind its side information -- LAME switches the tag off silently where it does not, here
+    // the stream is refused -- and the flush of a non-integer-ratio stream is partly host stand-ins with a fractional padding: no totals to report
+    if (ts.tag.on) {
+        InfoTagCfg& G = ts.tag;
+        if (G.on != 1) { set_err("Info tag: info_tag is 0 or 1"); ts.bad_option = true; return false; }
+        if (T.rs_frac) { set_err("the Info tag cannot be combined with fractionalResample (the flush's frames are partly host stand-ins and its padding is fractional)"); ts.bad_option = true; return false; }
+        G.size = T.out_samplerate > 0 ? (int)(((int64_t)(T.version + 1) * 72000 * T.brate) / T.out_samplerate) : 0;
+        if (T.sideinfo_len + TAG_BODY_BYTES > G.size || G.size > TAG_MAX_FRAME) {
+            set_err("Info tag: a frame of " + std::to_string(G.size) + " bytes cannot hold the tag (" + std::to_string(T.sideinfo_len) + " bytes of header and side information + " +
+                    std::to_string((int)TAG_BODY_BYTES) + ", at most " + std::to_string((int)TAG_MAX_FRAME) + ")");
+            ts.bad_option = true; return false;
+        }
     }
     return true;
 }

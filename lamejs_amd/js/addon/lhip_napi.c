@@ -43,6 +43,8 @@ static int (*p_state_set)(lhip_stream*, const void*, size_t);
 static size_t (*p_seek_tail)(const lhip_stream*);
 static int (*p_seek)(lhip_stream*, int64_t, const int16_t*, const int16_t*);
 static int64_t (*p_call_limit)(const lhip_stream*);
+static int (*p_stream_info)(const lhip_stream*, lhip_stream_info_t*);
+static int64_t (*p_info_tag)(lhip_stream*, uint8_t*, size_t);
 
 static int load_lib(napi_env env) {
     if (g_lib) return 1;
@@ -65,6 +67,7 @@ static int load_lib(napi_env env) {
     SYM(p_state_bytes, "lhip_state_bytes") SYM(p_state_get, "lhip_state_get") SYM(p_state_set, "lhip_state_set")
     SYM(p_seek_tail, "lhip_seek_tail_samples") SYM(p_seek, "lhip_seek") SYM(p_out_bytes, "lhip_encode_output_bytes")
     SYM(p_call_limit, "lhip_frac_call_limit") SYM(p_encode_pcm, "lhip_encode_pcm") SYM(p_encode_batch_pcm, "lhip_encode_batch_pcm")
+    SYM(p_stream_info, "lhip_stream_info") SYM(p_info_tag, "lhip_info_tag")
 #undef SYM
     return 1;
 }
@@ -291,6 +294,34 @@ static napi_value js_call_limit(napi_env env, napi_callback_info info) {
     napi_create_int64(env, p_call_limit(s), &r);
     return r;
 }
+/* { infoTag } streams (include/lamejs_hip.h, "Info tag"): the stream's totals as an object, and -- after flush() -- the finished tag frame.  Both throw
+ * on failure (a stream built without the option, a stream that has not been flushed or was moved). */
+static napi_value js_stream_info(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1], r, v;
+    napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
+    lhip_stream* s = argc >= 1 ? handle_arg(env, argv[0]) : NULL;
+    if (!s) return NULL;
+    lhip_stream_info_t si;
+    if (p_stream_info(s, &si) != 0) { napi_throw_error(env, NULL, p_last_error()); return NULL; }
+    napi_create_object(env, &r);
+    napi_create_int64(env, si.frames, &v); napi_set_named_property(env, r, "frames", v);
+    napi_create_int64(env, si.audio_bytes, &v); napi_set_named_property(env, r, "audioBytes", v);
+    napi_create_uint32(env, si.music_crc, &v); napi_set_named_property(env, r, "musicCrc", v);
+    napi_create_int32(env, si.delay, &v); napi_set_named_property(env, r, "delay", v);
+    napi_create_int32(env, si.padding, &v); napi_set_named_property(env, r, "padding", v);
+    napi_create_int32(env, si.tag_bytes, &v); napi_set_named_property(env, r, "tagBytes", v);
+    return r;
+}
+static napi_value js_info_tag(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
+    lhip_stream* s = argc >= 1 ? handle_arg(env, argv[0]) : NULL;
+    if (!s) return NULL;
+    uint8_t out[2880];
+    const int64_t n = p_info_tag(s, out, sizeof out);
+    if (n < 0) { napi_throw_error(env, NULL, p_last_error()); return NULL; }
+    return make_i8(env, out, (size_t)n);
+}
 static napi_value js_seek_tail(napi_env env, napi_callback_info info) {
     size_t argc = 1; napi_value argv[1], r;
     napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
@@ -348,7 +379,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"encodeBatch", 0, js_encode_batch, 0, 0, 0, napi_default, 0}, {"flushBatch", 0, js_flush_batch, 0, 0, 0, napi_default, 0},
         {"setDevices", 0, js_set_devices, 0, 0, 0, napi_default, 0},
         {"seekTailSamples", 0, js_seek_tail, 0, 0, 0, napi_default, 0}, {"callLimit", 0, js_call_limit, 0, 0, 0, napi_default, 0}, {"seek", 0, js_seek, 0, 0, 0, napi_default, 0},
-        {"stateGet", 0, js_state_get, 0, 0, 0, napi_default, 0}, {"stateSet", 0, js_state_set, 0, 0, 0, napi_default, 0}};
+        {"stateGet", 0, js_state_get, 0, 0, 0, napi_default, 0}, {"stateSet", 0, js_state_set, 0, 0, 0, napi_default, 0},
+        {"streamInfo", 0, js_stream_info, 0, 0, 0, napi_default, 0}, {"infoTag", 0, js_info_tag, 0, 0, 0, napi_default, 0}};
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;
 }

@@ -31,6 +31,12 @@
  * same frame sizes, two more bytes of side information per frame, a CRC-16 as ISO 11172-3 defines it.  copyright: true, original: false,
  * privateBit: true and emphasis: 0 | 1 | 3 set the header bits of those names; any other value (emphasis 2 is reserved) is a RangeError.  Accepted
  * wherever { downmix } is, encodeBatch() of protected and unprotected encoders included; not with a { fractionalResample } stream that resamples.
+ * Extension { infoTag: true }: the encoder writes a FILE, as LAME does: the first call that returns anything returns, in front of its audio, the placeholder of
+ * an Info/LAME tag frame (a valid header, then zeros; the audio behind it is byte for byte the stream without the option); enc.streamInfo() gives
+ * { frames, audioBytes, musicCrc, delay, padding (-1 before flush()), tagBytes }; after flush(), enc.infoTagFrame() returns the finished frame -- frame and byte
+ * counts, a 100-point seek table, encoder delay and end padding for gapless playback, the CRC-16 of the audio, LAME's extension fields -- as an Int8Array
+ * to be written over the placeholder at offset 0.  With every option above, encodeBatch() of tagged beside untagged encoders and { pendingFrames }
+ * included; refused at construction where a frame is too small to hold the tag (8 kHz at 8 kbps, say) and on a { fractionalResample } stream that resamples.
  * Extension { fractionalResample: true }: the 49 (channels, sample rate, kbps) triples the reference resamples by a non-integer ratio -- refused
  * by default, because the reference feeds itself NaN samples there once a call is long enough -- are accepted as call-sequence streams: every
  * encodeBuffer() gives the reference's bytes for the same sequence of call lengths; a call longer than the reference consumes whole throws
@@ -63,7 +69,7 @@ const blobCache = new Map();
 function tablesBlob(channels, samplerate, kbps, opts) {
     const key = [channels, samplerate, kbps, opts && opts.jointStereo ? 1 : 0, opts && opts.reservoir ? 1 : 0, opts && opts.fractionalResample ? 1 : 0,
         opts && opts.downmix ? 1 : 0, opts ? String(opts.scale) : '', opts ? String(opts.scaleLeft) : '', opts ? String(opts.scaleRight) : '',
-        opts ? ['protect', 'copyright', 'original', 'privateBit', 'emphasis'].map((k) => String(opts[k])).join(',') : ''].join('|');     /* (pendingFrames is host-side only) */
+        opts ? ['protect', 'copyright', 'original', 'privateBit', 'emphasis'].map((k) => String(opts[k])).join(',') : '', opts && opts.infoTag ? 1 : 0].join('|');     /* (pendingFrames is host-side only) */
     let blob = blobCache.get(key);
     if (!blob) { blob = tables.buildBlob(channels, samplerate, kbps, opts).blob; blobCache.set(key, blob); }
     return blob;
@@ -161,6 +167,9 @@ function Mp3Encoder(channels, samplerate, kbps, opts) {
     this.setState = function (state) { noPending('setState'); native.stateSet(handle, state); };
     /* { fractionalResample }: the encodeBuffer() length that is accepted whatever calls came before (0: any length goes) */
     this.callLimit = function () { return native.callLimit(handle); };
+    /* { infoTag }: the stream's totals so far; after flush() the finished Info/LAME tag frame, to be written over the placeholder at offset 0 */
+    this.streamInfo = function () { return native.streamInfo(handle); };
+    this.infoTagFrame = function () { noPending('infoTagFrame'); return native.infoTag(handle); };
 }
 
 /* RIFF/WAVE header reader with the reference's field names (index.js:138-193) */

@@ -240,6 +240,11 @@ function resolveParams(channels, samplerate, kbps, opts) {
             if (p.rs_filter_l == 31) throw new Error('lamejs_amd: { protect } and { fractionalResample } cannot be combined for (' + channels + ',' + samplerate + ',' + kbps + ')');
             p.sideinfo_len += 2;
         }
+        /* extension { infoTag }: the stream starts with room for the Info/LAME tag frame and the library keeps the totals the tag reports (frames, bytes,
+         * seek table, music CRC, delay and padding); the frame itself is written by the host once the stream has been flushed.  The flush of a
+         * non-integer-ratio stream is partly host stand-ins and its padding fractional: lhip_create refuses the tag there (-3), as it refuses a
+         * configuration whose frames are too small to hold it */
+        p.info_tag = flag('infoTag', 0);
     }
 
     /* CBR: ABR preset row for this bitrate (Lame.js:1202-1230, Presets.js:270-357) */
@@ -675,6 +680,25 @@ function buildBlob(channels, samplerate, kbps, opts) {
         Object.assign(cfg_i, { channels_in: p.channels_in, do_scale: p.do_scale, do_scale_left: p.do_scale_left, do_scale_right: p.do_scale_right });
         Object.assign(cfg_d, { scale_left: p.scale_left, scale_right: p.scale_right });
     }
+    /* { infoTag }: what the tag frame reports besides the stream's totals, resolved here as putLameVBR does (VBRTag.js:576-732) -- named entries that
+     * exist only with the option (a blob without it is the bytes it always was).  quality: 100 - 10 VBR_q - quality with lame_init's VBR_q = 4 and
+     * the wrapper's quality 3; method 1 (CBR); lowpass in units of 100 Hz; flags: ATHtype + (exp_nspsytune << 4), i.e. the nspsytune and the
+     * safe-joint bit; misc: noise_shaping + (stereoMode << 2) + (nonOptimal << 5) + (sourceFreq << 6) by VBRTag.js:686-732 -- a downmix is MONO,
+     * unequal channel gains, a disabled reservoir below 320 kbps and an input rate of at most 32 kHz are "non-optimal"; preset: the bitrate that
+     * selected the ABR preset row (Lame.js:1216-1218, Presets.js:415); delay: Encoder.ENCDELAY */
+    let tagVersion = null;
+    if (p.info_tag) {
+        const VBR_q = 4, quality = 3;
+        const stereoMode = p.mode == MODE_MONO ? 0 : p.mode == MODE_STEREO ? 1 : 3;
+        const sourceFreq = samplerate <= 32000 ? 0 : samplerate == 48000 ? 2 : samplerate > 48000 ? 3 : 1;
+        const nonOptimal = (p.scale_left < p.scale_right || p.scale_left > p.scale_right || (p.disable_reservoir && p.brate < 320) || p.ATHtype == 0 || samplerate <= 32000) ? 1 : 0;
+        const lp = p.lowpassfreq / 100.0 + .5;
+        Object.assign(cfg_i, { info_tag: 1, tag_quality: Math.max(0, 100 - 10 * VBR_q - quality), tag_method: 1, tag_lowpass: 0 | (lp > 255 ? 255 : lp),
+            tag_flags: (p.ATHtype + (p.exp_nspsytune << 4)) & 0xff, tag_misc: (p.noise_shaping + (stereoMode << 2) + (nonOptimal << 5) + (sourceFreq << 6)) & 0xff,
+            tag_preset: p.brate, tag_delay: 576 });
+        tagVersion = 'LAME' + C.lame_short_version.split('.').slice(0, 2).join('.') + 'r';          /* Version.js:56-59 getLameVeryShortVersion */
+        if (tagVersion.length != 9) throw new Error('lamejs_amd: the very short version string must have 9 characters');
+    }
     const entries = [];
     entries.push(['cfg_i_names', Int32Array.from(Buffer.from(Object.keys(cfg_i).join(',') + '\0', 'ascii'))]);
     entries.push(['cfg_i', I(Object.values(cfg_i))]);
@@ -710,6 +734,7 @@ function buildBlob(channels, samplerate, kbps, opts) {
     huffmanEntries().forEach(e => entries.push(e));
     /* what the blob was generated FROM: the first 8 bytes of sha256(tables.js ++ constants.json) -- a cached blob is stale when its generator
      * has changed, whatever the files' modification times say after a checkout (lamejs_amd/__init__.py tables_blob, __graft_entry__.py) */
+    if (tagVersion) push('tag_version', I(tagVersion.split('').map(ch => ch.charCodeAt(0))));
     push('src_sha256_64', sourceHash());
     return { blob: packBlob(entries), params: p, tables: T };
 }
@@ -734,12 +759,12 @@ module.exports = { buildBlob, resolveParams, buildTables, packBlob, sourceHash, 
 
 if (require.main === module) {
     /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] [fracresample] [downmix] [scale=G] [scaleLeft=G] [scaleRight=G]
-     *      [protect] [copyright] [original=0|1] [privateBit] [emphasis=E] */
+     *      [protect] [copyright] [original=0|1] [privateBit] [emphasis=E] [infoTag] */
     const [ch, sr, kb, out] = process.argv.slice(2), flags = process.argv.slice(6);
     const opts = { jointStereo: flags.includes('joint'), reservoir: flags.includes('reservoir'), fractionalResample: flags.includes('fracresample') };
     if (flags.includes('downmix')) opts.downmix = true;
     for (const f of flags) { const m = /^(scale|scaleLeft|scaleRight)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
-    for (const k of ['protect', 'copyright', 'privateBit']) if (flags.includes(k)) opts[k] = true;
+    for (const k of ['protect', 'copyright', 'privateBit', 'infoTag']) if (flags.includes(k)) opts[k] = true;
     for (const f of flags) { const m = /^(original|emphasis)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
     const r = buildBlob(+ch, +sr, +kb, opts);
     require('fs').writeFileSync(out, r.blob);
