@@ -38,6 +38,8 @@
  *
  * Sample formats.  lhip_encode takes Int16 planes; lhip_encode_pcm and the *_pcm batch entries take Int16 or Float32, planar or interleaved
  * (see LHIP_PCM_* below): Float32 is what the reference itself encodes, so fractional samples and samples beyond 16 bits give its bytes.
+ * They also take what a WAV file stores -- 8-bit unsigned, packed 24-bit, 32-bit integers, floats and doubles in [-1, 1] -- and doubles used as
+ * given; a kernel of its own (g_ingest) turns those into Float32 planes in front of the call's first reader, so no host-side pass widens them.
  *
  * Input gains and downmix (extension).  A blob built with { downmix, scale, scaleLeft, scaleRight } (tables.js) carries the reference's
  * gfp.scale / scale_left / scale_right and, for a downmix, MPEGMode.MONO with two input channels (Lame.js:1551-1584).  lhip_config.channels
@@ -160,6 +162,28 @@ int64_t lhip_encode(lhip_stream* s, const int16_t* left, const int16_t* right, s
 #define LHIP_PCM_S16         0
 #define LHIP_PCM_F32         1
 #define LHIP_PCM_INTERLEAVED 2
+/* Sample types of WAV files (extension).  The sample type of a format is `format & ~LHIP_PCM_INTERLEAVED`; INTERLEAVED may be or-ed to each.  A type is
+ * defined by the number the reference would find in its Float32 buffer had the caller widened the samples for it:
+ *   U8    1 byte, unsigned                          (b - 128) * 256, exact
+ *   S24   3 bytes, little-endian, packed            v / 256, exact in Float32; any address
+ *   S32   int32                                     (float)(v / 65536.0): one rounding, to nearest even
+ *   F32N  float in [-1, 1]                          x * 32768
+ *   F64N  double in [-1, 1]                         (float)(x * 32768.0): one rounding
+ *   F64   double, used as given                     (float)x: what a Float64Array handed to the reference becomes
+ * The Float32 contract follows the conversion: the value must be finite with |v| <= the stream's limit (131072, less where its gains exceed 1); F64N and
+ * F64 are compared before their rounding, so a double above the limit is refused even where it would round onto it.  Host-pointer entries refuse such a
+ * call with -4 (stream, channel, index and value in lhip_last_error()) and consume nothing; the device-pointer entry reads such a sample as 0.0f and counts
+ * it in lhip_last_batch_rejected_samples().  Integer types cannot leave the contract and are never scanned.  Device pointers of the 4- and 8-byte types
+ * among these must be multiples of the element size (-4 with a message otherwise); U8 and S24 may lie at any address.  A format whose type is none of the
+ * values defined here returns -4.  A stream may change type from call to call; state blobs, lhip_seek's Int16 tails and the output-size entries do not
+ * depend on the type.  A call in one of these types is converted once into Float32 planes of the device context (the kernel g_ingest, LHIP_PATH_INGEST;
+ * a host call small enough for one pinned block is converted by the host while it fills that block) and is a Float32 planar call from there on. */
+#define LHIP_PCM_U8          4
+#define LHIP_PCM_S24         8
+#define LHIP_PCM_S32         12
+#define LHIP_PCM_F32N        16
+#define LHIP_PCM_F64N        20
+#define LHIP_PCM_F64         24
 int64_t lhip_encode_pcm(lhip_stream* s, int format, const void* left, const void* right, size_t nsamples,
                         uint8_t* out, size_t out_cap);
 
@@ -250,6 +274,9 @@ void lhip_last_batch_stats(int64_t* frames, int64_t* repaired_frames, int64_t* r
 /* (one more bit, stated as a shift: OUT_CRC 0x2000 -- the batch held { infoTag } streams and their music CRC was computed by the kernel g_out_crc; such a
  *  batch without this bit took the host's CRC over the pinned mirror of a SMALL_CALL) */
 #define LHIP_PATH_OUT_CRC (1u << 13)
+/* (and INGEST 0x4000: samples of a LHIP_PCM_U8 .. LHIP_PCM_F64 call were turned into Float32 planes by the kernel g_ingest; such a call without this bit was a
+ *  SMALL_CALL, converted by the host) */
+#define LHIP_PATH_INGEST (1u << 14)
 int lhip_debug_last_paths(uint32_t* mask);
 
 /* Info tag (extension; see above).  What a stream built with { infoTag } has put out so far, and the finished tag frame. */
@@ -273,6 +300,11 @@ int64_t lhip_info_tag(lhip_stream* s, uint8_t* out, size_t cap);
 size_t lhip_debug_crc_span(void);
 int lhip_debug_crc16(const void* bytes, size_t n, size_t misalign, uint32_t* crc);
 int lhip_debug_info_toc(const int64_t* frames, size_t ncalls, int kbps, uint8_t* toc);
+/* Test hook.  lhip_debug_ingest: THE KERNEL g_ingest (in the simulation libraries: its body) over the caller's samples in `format` (one of the LHIP_PCM_U8 ..
+ * LHIP_PCM_F64 types, optionally INTERLEAVED), placed misalign (0 .. 15) bytes past a 16-byte boundary of a device buffer of exactly that size: channels (1 or
+ * 2) * nsamples elements -- interleaved, or the left plane followed by the right one.  left / right (right: two channels only) receive nsamples floats each,
+ * *rejected the samples read as zero (limit 131072).  misalign must be a multiple of the element size for the 4- and 8-byte types.  Returns 0 or < 0. */
+int lhip_debug_ingest(int format, int channels, const void* bytes, size_t nsamples, size_t misalign, float* left, float* right, int64_t* rejected);
 
 /* Debug/test taps (tests only): copy intermediate results of the most recent batch to the host.
  * what: 0 xr [granule][ch][576] f32, 1 blocktype [granule][ch] i32, 2 E [granule][psy ch][122] f32 (psy ch = ch, or L R mid side in joint stereo; thresholds

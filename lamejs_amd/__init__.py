@@ -22,13 +22,16 @@ _PKG = Path(__file__).resolve().parent
 _LIB_PATH = _PKG / "lib" / "liblamejs_hip.so"
 _TABLE_DIR = _PKG / "tables"
 
-__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED", "PATH_NAMES", "PATH_NAMES_ALL", "last_batch_paths", "StreamInfo"]
+__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED", "PATH_NAMES", "PATH_NAMES_ALL", "PATH_BITS", "last_batch_paths", "StreamInfo",
+           "PCM_U8", "PCM_S24", "PCM_S32", "PCM_F32N", "PCM_F64N", "PCM_F64", "PCM_BYTES"]
 
 # launch paths of a batch (include/lamejs_hip.h: LHIP_PATH_*), in bit order
 PATH_NAMES = ("FRAME", "FRAME_RESV", "SEPARATE", "PREP", "PSY4", "QUANT_PAIR", "QUANT_PERSISTENT", "RESV_STREAM_HELPERS", "RESV_STREAM_NOHELPERS",
               "RESV_FLUSH", "FIXUP_SINGLE", "FIXUP_COOP", "SMALL_CALL")
-# ... and the bit the header states as a shift: OUT_CRC (the music CRC of ``info_tag`` streams came from the kernel g_out_crc, not from the host)
-PATH_NAMES_ALL = PATH_NAMES + ("OUT_CRC",)
+# every bit in bit order: the ones above, then those the header states as shifts -- OUT_CRC (the music CRC of ``info_tag`` streams came from the kernel
+# g_out_crc, not from the host) and INGEST (samples of a WAV sample type were turned into Float32 planes by the kernel g_ingest, not by the host)
+PATH_BITS = PATH_NAMES + ("OUT_CRC", "INGEST")
+PATH_NAMES_ALL = PATH_BITS[:14]      # (the names up to OUT_CRC, kept for callers that index it)
 
 
 def last_batch_paths(lib=None) -> frozenset:
@@ -38,13 +41,17 @@ def last_batch_paths(lib=None) -> frozenset:
     rc = lib.lhip_debug_last_paths(ctypes.byref(m))
     if rc != 0:
         raise LhipError(f"lhip_debug_last_paths failed ({rc}): {lib.lhip_last_error().decode()}")
-    if m.value >> len(PATH_NAMES_ALL):
+    if m.value >> len(PATH_BITS):
         raise LhipError(f"lhip_debug_last_paths: unknown bits in {m.value:#x}")
-    return frozenset(n for i, n in enumerate(PATH_NAMES_ALL) if m.value >> i & 1)
+    return frozenset(n for i, n in enumerate(PATH_BITS) if m.value >> i & 1)
 
 
 # sample formats of the *_pcm entries (include/lamejs_hip.h: LHIP_PCM_*): a sample type, optionally or-ed with PCM_INTERLEAVED
 PCM_S16, PCM_F32, PCM_INTERLEAVED = 0, 1, 2
+# ... and the sample types a WAV file stores: 8-bit unsigned, packed 24-bit, 32-bit integers, float / double in [-1, 1], double used as given
+PCM_U8, PCM_S24, PCM_S32, PCM_F32N, PCM_F64N, PCM_F64 = 4, 8, 12, 16, 20, 24
+# bytes per sample of a sample type
+PCM_BYTES = {PCM_S16: 2, PCM_F32: 4, PCM_U8: 1, PCM_S24: 3, PCM_S32: 4, PCM_F32N: 4, PCM_F64N: 8, PCM_F64: 8}
 
 
 class LhipError(RuntimeError):
@@ -108,6 +115,7 @@ ABI = {
     "lhip_debug_crc_span": (_size, []),
     "lhip_debug_crc16": (_int, [_ptr, _size, _size, ctypes.POINTER(ctypes.c_uint32)]),
     "lhip_debug_info_toc": (_int, [_ptr, _size, _int, _ptr]),
+    "lhip_debug_ingest": (_int, [_int, _int, _ptr, _size, _size, _ptr, _ptr, _pi64]),
     "lhip_last_error": (ctypes.c_char_p, []),
     "lhip_version": (ctypes.c_char_p, []),
 }
@@ -231,6 +239,14 @@ def _as_pcm(a):
     return _as_i16(arr), PCM_S16
 
 
+def _as_raw(data) -> np.ndarray:
+    """``bytes`` or a 1-D ``uint8`` array, as a contiguous ``uint8`` array; anything else is refused (no cast: an Int16 array is not raw bytes)."""
+    a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data)
+    if a.dtype != np.uint8 or a.ndim != 1:
+        raise ValueError("raw PCM must be bytes or a 1-D uint8 array")
+    return np.ascontiguousarray(a)
+
+
 def _same_type(arrs):
     """Arrays of one call share one sample type: Float32 if any of them is floating (Int16 values are exact in Float32)."""
     pairs = [_as_pcm(a) for a in arrs]
@@ -348,6 +364,25 @@ class Mp3Encoder:
             raise ValueError("interleaved PCM: the length is not a multiple of the channel count")
         return self._encode(fmt | PCM_INTERLEAVED, a, a, len(a) // self.channels)
 
+    def encode_pcm(self, data, fmt, interleaved=True) -> bytes:
+        """Extension: PCM as a WAV file stores it.  ``data``: a ``bytes`` object or a ``uint8`` array holding samples of the type ``fmt`` (``PCM_U8``,
+        ``PCM_S16``, ``PCM_S24``, ``PCM_S32``, ``PCM_F32N``, ``PCM_F64N``; also ``PCM_F32`` / ``PCM_F64``: values used as given) -- interleaved
+        (L R L R ..., as in the file), or with ``interleaved=False`` the left plane followed by the right one.  The bytes travel as they are and
+        the kernel g_ingest converts them; only a call small enough for one pinned block (a few frames) is converted by the host while it fills
+        that block.  Integer types are never looked at on the host; a call of a float type is scanned first, and a sample outside the contract
+        raises and consumes nothing."""
+        fmt = int(fmt)
+        if fmt not in PCM_BYTES:
+            raise ValueError(f"unknown sample type {fmt}")
+        a = _as_raw(data)
+        unit = PCM_BYTES[fmt] * self.channels
+        if len(a) % unit:
+            raise ValueError("encode_pcm: the length is not a whole number of sample frames")
+        n = len(a) // unit
+        if interleaved or self.channels == 1:
+            return self._encode(fmt | (PCM_INTERLEAVED if self.channels == 2 else 0), a, a, n)
+        return self._encode(fmt, a, a[n * PCM_BYTES[fmt]:], n)
+
     def _encode(self, fmt, l, r, nsamples) -> bytes:
         if nsamples == 0:
             return b""
@@ -396,24 +431,37 @@ class Mp3Encoder:
             pass
 
 
-def encode_streams(encoders, lefts, rights=None, flush=True, interleaved=False):
+def encode_streams(encoders, lefts, rights=None, flush=True, interleaved=False, fmt=None):
     """Batch extension (BASELINE config 5): one launch for many independent streams.
 
     encoders: list of Mp3Encoder with identical configuration (``fractional_resample`` streams may mix configurations); lefts/rights: per-stream arrays.
     Int16 if every array is of an integer dtype, otherwise the whole batch as Float32 -- still one launch.  ``interleaved``: ``lefts[i]``
     holds ``channels * n`` samples (L R L R ...), ``rights`` is ignored.
+    ``fmt``: a sample type (``PCM_U8`` ... ``PCM_F64``; ``PCM_BYTES``): the arrays are ``bytes`` / ``uint8`` arrays of samples of that type, as
+    ``Mp3Encoder.encode_pcm`` takes them (planar: ``lefts[i]`` and ``rights[i]`` one plane each).
     Returns a list of bytes objects (encode [+ flush] output per stream)."""
     lib = encoders[0]._lib
     n = len(encoders)
-    arrs, fmt = _same_type(list(lefts) + ([] if rights is None or interleaved else list(rights)))
-    L = arrs[:n]
-    R = L if len(arrs) == n else arrs[n:]
+    if fmt is not None:
+        fmt = int(fmt)
+        if fmt not in PCM_BYTES:
+            raise ValueError(f"unknown sample type {fmt}")
+        L = [_as_raw(a) for a in lefts]
+        R = L if rights is None or interleaved else [_as_raw(a) for a in rights]
+        unit = [PCM_BYTES[fmt] * (e.channels if interleaved else 1) for e in encoders]
+        if any(len(a) % u for a, u in zip(L, unit)) or any(len(a) != len(b) for a, b in zip(L, R)):
+            raise ValueError("encode_streams: an array is not a whole number of sample frames, or left / right differ in length")
+        counts = [len(a) // u for a, u in zip(L, unit)]
+    else:
+        arrs, fmt = _same_type(list(lefts) + ([] if rights is None or interleaved else list(rights)))
+        L = arrs[:n]
+        R = L if len(arrs) == n else arrs[n:]
+        counts = [len(a) // e.channels if interleaved else len(a) for e, a in zip(encoders, L)]
     if interleaved:
         fmt |= PCM_INTERLEAVED
     H = (ctypes.c_void_p * n)(*[e._h for e in encoders])
     lp = (ctypes.c_void_p * n)(*[a.ctypes.data for a in L])
     rp = (ctypes.c_void_p * n)(*[a.ctypes.data for a in R])
-    counts = [len(a) // e.channels if interleaved else len(a) for e, a in zip(encoders, L)]
     ns = (ctypes.c_size_t * n)(*counts)
     caps = [lib.lhip_max_output_bytes(e._h, c) for e, c in zip(encoders, counts)]
     outs = [np.empty(c, dtype=np.uint8) for c in caps]

@@ -18,6 +18,7 @@
 #endif
 #include "k_bits.h"
 #include "k_crc.h"
+#include "k_ingest.h"
 
 #include <string>
 #include <vector>
@@ -31,6 +32,10 @@
 #include <cstdio>
 #include <chrono>
 #include <cmath>
+#if defined(LHIP_HOSTSIM) && defined(__SANITIZE_ADDRESS__)
+#include <sanitizer/asan_interface.h>      // lhip_debug_ingest poisons the bytes in front of its input (tests/tools/wavpcm_bounds.c)
+#define LHIP_ASAN_POISON 1
+#endif
 
 using namespace lhip;
 
@@ -285,8 +290,20 @@ static int encode_many(lhip_stream* const* streams, size_t n, int format, const 
         if (!streams[i] || streams[i]->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
         if (streams[i]->ctx != streams[0]->ctx) { set_err("batch: streams on different devices"); return LHIP_ERR_INTERNAL; }
         jobs[i] = Job{streams[i], l[i], r ? r[i] : nullptr, ns[i], out[i], cap[i], 0, 0, 0, 0};
-        jobs[i].f32 = format & LHIP_PCM_F32; jobs[i].inter = (format & LHIP_PCM_INTERLEAVED) != 0;
-        jobs[i].count_rejected = dev_io && jobs[i].f32;
+        jobs[i].set_format(format);
+        jobs[i].count_rejected = dev_io && (jobs[i].f32 || (fmt_ingest(jobs[i].type) && ingest_is_float(jobs[i].type)));
+        // WAV sample types by device pointer: the kernel reads 4- and 8-byte elements as such (U8 and S24 lie anywhere)
+        if (dev_io && fmt_ingest(jobs[i].type) && fmt_bps(jobs[i].type) >= 4 && ns[i] > 0) {
+            const uintptr_t m = (uintptr_t)fmt_bps(jobs[i].type) - 1;
+            const bool two = streams[i]->ts->T.channels_in == 2 && !jobs[i].inter && jobs[i].r;
+            if (((uintptr_t)jobs[i].l & m) || (two && ((uintptr_t)jobs[i].r & m))) {
+                char txt[160];
+                snprintf(txt, sizeof txt, "stream %zu: device pointer of a %zu-byte sample type is not a multiple of %zu; nothing was consumed", i, m + 1, m + 1);
+                set_err(txt);
+                for (size_t k = 0; k < n; k++) if (written) written[k] = LHIP_ERR_INTERNAL;
+                return LHIP_ERR_INTERNAL;
+            }
+        }
     }
     // Bit reservoir (extension): the frames of a stream are a serial chain, walked by one workgroup per stream inside the launch
     // (g_resv_stream); a stream that ends with this call (flush) has its bitstream padded by the same launch -- decided per stream
@@ -379,7 +396,7 @@ int lhip_encode_batch_pcm(lhip_stream* const* streams, size_t nstreams, int form
 static int encode_batch_pcm_inner(lhip_stream* const* streams, size_t nstreams, int format, const void* const* left, const void* const* right,
                                   const size_t* nsamples, uint8_t* const* out, const size_t* out_cap, int64_t* written) {
     if (!fmt_ok(format)) { set_err("unknown sample format"); return LHIP_ERR_INTERNAL; }
-    if ((format & LHIP_PCM_F32) && streams && left && nsamples)       // every stream's samples are looked at before any stream consumes anything
+    if (fmt_scanned(format) && streams && left && nsamples)       // every stream's samples are looked at before any stream consumes anything
         for (size_t i = 0; i < nstreams; i++)
             if (streams[i] && streams[i]->magic == 0x4c484950 && !host_samples_ok(i, streams[i]->ts->T.channels_in, streams[i]->ts->T.pcm_limit, format, left[i], right ? right[i] : nullptr, nsamples[i])) {
                 for (size_t k = 0; k < nstreams; k++) if (written) written[k] = LHIP_ERR_INTERNAL;
@@ -743,6 +760,66 @@ int lhip_debug_crc16(const void* bytes, size_t n, size_t misalign, uint32_t* crc
         *crc = r & 0xffff;
     } else set_err("hipMalloc failed");
     rt::dfree(buf); rt::dfree(aux);
+    return ok ? 0 : LHIP_ERR_INTERNAL;
+}
+// Test hook.  lhip_debug_ingest: the kernel g_ingest (in the simulations: its body) over the caller's samples, in a device buffer that ends with them and
+// starts `misalign` bytes in front of them past a 16-byte boundary; the planes are buffers of exactly nsamples floats.
+int lhip_debug_ingest(int format, int channels, const void* bytes, size_t nsamples, size_t misalign, float* left, float* right, int64_t* rejected) {
+    const int type = fmt_type(format);
+    if (!fmt_ok(format) || !fmt_ingest(type) || (channels != 1 && channels != 2) || (!bytes && nsamples) || !left || (channels == 2 && !right) || !rejected || misalign > 15 ||
+        nsamples > (size_t)1 << 31 || (fmt_bps(type) >= 4 && misalign % fmt_bps(type))) { set_err("lhip_debug_ingest: bad argument"); return LHIP_ERR_INTERNAL; }
+    if (rt::device_count() <= 0) { set_err("no HIP device available (this library has no CPU fallback)"); return LHIP_ERR_INTERNAL; }
+    const size_t bps = fmt_bps(type), nb = nsamples * bps * (size_t)channels;
+    const bool il = (format & LHIP_PCM_INTERLEAVED) && channels == 2;
+    *rejected = 0;
+    if (nsamples == 0) return 0;
+    // [16 bytes | misalign bytes | the samples]: the block ends with the samples; in a simulation built with AddressSanitizer everything in front of them that
+    // can be poisoned is (whole 8-byte granules: the piece in front of the window, and the first half of the head piece where misalign >= 8), so a wide load
+    // of the ragged head is seen as well as one past the tail.  One block per plane, exactly nsamples floats: a store past the left plane is not in the right one.
+    uint8_t* buf = (uint8_t*)rt::dmalloc(16 + misalign + nb);          // (device allocations are 256-byte aligned; the simulations': 16)
+    float* pl = (float*)rt::dmalloc(nsamples * 4);
+    float* pr = channels == 2 ? (float*)rt::dmalloc(nsamples * 4) : nullptr;
+    uint8_t* aux = (uint8_t*)rt::dmalloc(sizeof(IngestDesc) + 16);
+    bool ok = buf && pl && (pr || channels == 1) && aux && ((uintptr_t)buf & 15) == 0;
+    uint8_t* const smp = buf ? buf + 16 + misalign : nullptr;
+#if defined(LHIP_HOSTSIM) && defined(LHIP_ASAN_POISON)
+    if (ok) ASAN_POISON_MEMORY_REGION(buf, 16 + (misalign & ~(size_t)7));
+#endif
+    if (ok) {
+        IngestDesc d; memset(&d, 0, sizeof d);
+        d.type = type; d.blk0 = 0; d.inter = il ? 1 : 0; d.narr = (channels == 2 && !il) ? 2 : 1;
+        d.src[0] = smp; d.src[1] = d.narr == 2 ? smp + nsamples * bps : nullptr;
+        d.dst[0] = pl; d.dst[1] = channels == 2 ? pr : pl;
+        d.nelem = (int64_t)nsamples * (il ? 2 : 1); d.tiles = ingest_tiles(type, d.nelem);
+        const int grid = (int)(d.tiles * d.narr);
+        IngestDesc* dD = (IngestDesc*)aux; unsigned long long* dC = (unsigned long long*)(aux + sizeof(IngestDesc));
+        unsigned long long zero = 0, cnt = 0;
+        ok = rt::h2d(smp, bytes, nb, nullptr) && rt::h2d(dD, &d, sizeof d, nullptr) && rt::h2d(dC, &zero, 8, nullptr) && rt::sync(nullptr);
+#ifndef LHIP_HOSTSIM
+        if (ok) {
+            hipLaunchKernelGGL(g_ingest, dim3(grid), dim3(64), 0, 0, (const IngestDesc*)dD, 1, PCM_F32_LIMIT, dC);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { set_err(std::string("g_ingest: ") + hipGetErrorString(e)); ok = false; }
+        }
+#else
+        if (ok) {
+            alignas(16) static thread_local uint8_t LI[ING_WINDOW];
+            for (int b = 0; b < grid; b++) {
+#ifdef LHIP_WAVESIM
+                wsim::run([&](int lane_) { const unsigned r = kb_ingest(dD, 0, b, lane_, LI, PCM_F32_LIMIT); if (lane_ == 0) *dC += r; });
+#else
+                *dC += kb_ingest(dD, 0, b, 0, LI, PCM_F32_LIMIT);
+#endif
+            }
+        }
+#endif
+        ok = ok && rt::d2h(left, pl, nsamples * 4, nullptr) && (channels == 1 || rt::d2h(right, pr, nsamples * 4, nullptr)) && rt::d2h(&cnt, dC, 8, nullptr) && rt::sync(nullptr);
+        *rejected = (int64_t)cnt;
+    } else set_err("hipMalloc failed");
+#if defined(LHIP_HOSTSIM) && defined(LHIP_ASAN_POISON)
+    if (buf) ASAN_UNPOISON_MEMORY_REGION(buf, 16 + misalign);
+#endif
+    rt::dfree(buf); rt::dfree(pl); rt::dfree(pr); rt::dfree(aux);
     return ok ? 0 : LHIP_ERR_INTERNAL;
 }
 int lhip_debug_info_toc(const int64_t* frames, size_t ncalls, int kbps, uint8_t* toc) {

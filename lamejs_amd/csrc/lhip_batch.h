@@ -14,10 +14,18 @@ struct Job {
     double rs_used = 0;         // non-integer ratio: num_used of the pass (== the call's length for every call that is accepted; a flush pass may end on a whole frame)
     int f32 = 0, inter = 0;     // sample format of l / r: Float32 (else Int16); interleaved (l holds channels * n samples, r is ignored)
     bool count_rejected = false;   // Float32 by device pointer from the caller: count the samples the read sites refuse
+    int type = 0;               // sample type of l / r (format & ~LHIP_PCM_INTERLEAVED); f32 == (type == LHIP_PCM_F32).  The WAV types (>= LHIP_PCM_U8) become Float32 planes first (k_ingest.h)
+    void set_format(int format) { type = format & ~LHIP_PCM_INTERLEAVED; f32 = type == LHIP_PCM_F32; inter = (format & LHIP_PCM_INTERLEAVED) != 0; }
 };
-// bytes per sample / the four formats of the C ABI
-static inline size_t fmt_bps(int f32) { return f32 ? 4 : 2; }
-static inline bool fmt_ok(int format) { return format >= 0 && format <= 3; }
+static_assert(LHIP_PCM_U8 == ING_U8 && LHIP_PCM_S24 == ING_S24 && LHIP_PCM_S32 == ING_S32 && LHIP_PCM_F32N == ING_F32N && LHIP_PCM_F64N == ING_F64N && LHIP_PCM_F64 == ING_F64, "k_ingest.h states the header's sample types");
+// bytes per sample of a sample type / the formats of the C ABI / the types that g_ingest (or, for a small host call, the host) turns into Float32 planes
+static inline size_t fmt_bps(int type) { return type == LHIP_PCM_S16 ? 2 : type == LHIP_PCM_F32 ? 4 : (size_t)ingest_bps(type); }
+static inline bool fmt_ok(int format) {
+    const int t = format & ~LHIP_PCM_INTERLEAVED;
+    return format >= 0 && (t == LHIP_PCM_S16 || t == LHIP_PCM_F32 || t == LHIP_PCM_U8 || t == LHIP_PCM_S24 || t == LHIP_PCM_S32 || t == LHIP_PCM_F32N || t == LHIP_PCM_F64N || t == LHIP_PCM_F64);
+}
+static inline int fmt_type(int format) { return format & ~LHIP_PCM_INTERLEAVED; }
+static inline bool fmt_ingest(int type) { return type >= LHIP_PCM_U8; }
 
 // resampling by the integer ratio r: output sample m exists once m*r + 16 < (input samples received) -- see kb_resample_elem
 static int64_t rs_outputs(int64_t n_in_total, int r) { return n_in_total > 16 ? (n_in_total - 16 + r - 1) / r : 0; }
@@ -113,6 +121,9 @@ struct CallLayout {
 struct BatchPlan {
     TableSet* ts = nullptr;
     bool dev_io = false, resv = false, count_rej = false, use_frame = false, small = false;
+    bool count_f32 = false;                        // ... of count_rej: Float32 samples, counted by g_count_rejected (the WAV float types are counted where they are converted)
+    // WAV sample types (k_ingest.h): streams whose samples g_ingest converts, its grid, the floats of all planes, the descriptors on the device
+    int ingest = 0, ingest_tiles = 0; size_t ingest_floats = 0; const IngestDesc* dING = nullptr;
     int S = 0, nfs = 0, ngs = 0, nfr = 0, maxF = 0;
     uint32_t paths = 0;                            // LHIP_PATH_*: one bit per launch decision run_pipeline really takes for this batch (host-side record only)
     int64_t pcm_plane = 0, in_total = 0, out_total = 0, repaired = 0, iters = 0;
@@ -165,8 +176,14 @@ static bool plan_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, BatchP
         if (j.F > P.maxF) P.maxF = j.F;
         P.pcm_plane += (total + 63) & ~(int64_t)63;
         P.in_total += (int64_t)j.n; P.out_total += (j.bytes + 15) & ~(int64_t)15;
-        P.in_bytes += (j.n * (size_t)Cin * fmt_bps(j.f32) + 3) & ~(size_t)3;
-        P.count_rej |= j.count_rejected && j.f32 && j.n > 0;
+        if (fmt_ingest(j.type)) {      // raw bytes travel, or (a small call) the Float32 planes the host makes of them: room for either, 16-byte aligned
+            const size_t b = fmt_bps(j.type);
+            P.in_bytes += (j.n * (size_t)Cin * (b > 4 ? b : 4) + 15) & ~(size_t)15;
+            if (j.n > 0) { P.ingest++; P.ingest_floats += (size_t)Cin * ((j.n + 3) & ~(size_t)3); }
+        } else
+        P.in_bytes += (j.n * (size_t)Cin * fmt_bps(j.type) + 3) & ~(size_t)3;
+        P.count_f32 |= j.count_rejected && j.f32 && j.n > 0;
+        P.count_rej |= j.count_rejected && (j.f32 || (fmt_ingest(j.type) && ingest_is_float(j.type))) && j.n > 0;
     }
     // at most one frame per stream: the whole frame program in one launch (kb_frame_stage); LAMEJS_HIP_NO_FRAME_KERNEL=1 keeps the separate kernels
     static const bool no_frame = []() { const char* e = getenv("LAMEJS_HIP_NO_FRAME_KERNEL"); return e && e[0] == '1'; }();
@@ -249,9 +266,21 @@ static bool stage_inputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P) {
         o.rs_p0 = T.rs_ratio <= 1 ? 0 : (int)(rs_outputs(j.s->rs_n_in, T.rs_ratio) * T.rs_ratio - 16 - j.s->rs_n_in);
         o.rs_itime = j.s->rs_itime;
         out_rel[i] = sd[i].out_off;
-        const size_t bps = fmt_bps(j.f32);
+        const size_t bps = fmt_bps(j.type);
         const bool il = j.inter && Cin == 2;          // (one channel: interleaved is planar)
+        const bool ing = fmt_ingest(j.type);
         o.f32 = j.f32 ? 1 : 0; o.stride = il ? 2 : 1;
+        if (ing && small) {          // a small call: the host converts while it fills the pinned block -- Float32 planes, no launch
+            uint8_t* base = smb + L.sm_in; uint8_t* hbase = pin + L.pin(L.sm_in);
+            float* h0 = (float*)(hbase + in_off); float* h1 = Cin == 2 ? h0 + j.n : nullptr;
+            const bool one = Cin == 2 && !il && (!j.r || j.r == j.l);          // right == left: the samples exist once
+            (void)ingest_host(j.type, j.l, j.r, j.n, one ? 1 : Cin, il, h0, h1, T.pcm_limit);
+            o.f32 = 1; o.stride = 1;
+            o.src[0] = base + in_off; o.src[1] = (Cin == 2 && !one) ? base + in_off + j.n * 4 : o.src[0];
+            in_off = (in_off + j.n * 4 * (size_t)Cin + 15) & ~(size_t)15;
+            o.out = smb + L.sm_out + sd[i].out_off;
+            continue;
+        }
         if (dev_io) {
             o.src[0] = j.l; o.src[1] = il ? (const void*)((const uint8_t*)j.l + bps) : ((Cin == 2 && j.r) ? j.r : j.l); o.out = j.out;
         } else {
@@ -269,9 +298,35 @@ static bool stage_inputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P) {
                 else if (!rt::h2d((void*)o.src[1], j.r ? j.r : j.l, plane, st)) return false;
                 in_off += plane;
             } else if (!il) o.src[1] = o.src[0];
-            in_off = (in_off + 3) & ~(size_t)3;
+            in_off = ing ? (in_off + 15) & ~(size_t)15 : (in_off + 3) & ~(size_t)3;
             o.out = (small ? smb + L.sm_out : (uint8_t*)ws.out8.p) + sd[i].out_off;
         }
+    }
+    // WAV sample types: o.src[] are the raw samples on the device by now; g_ingest's descriptors are made of them and the stream reads the planes instead
+    if (P.ingest && !small) {
+        if (!ws.ingest.ensure(P.ingest_floats * 4 + 64) || !ws.ingest_desc.ensure((size_t)S * sizeof(IngestDesc))) return false;
+        std::vector<IngestDesc> id((size_t)S);
+        float* plane = (float*)ws.ingest.p;
+        int64_t blk = 0;
+        for (int i = 0; i < S; i++) {
+            const Job& j = jobs[i]; StreamIO& o = io[i]; IngestDesc& d = id[i];
+            memset(&d, 0, sizeof d);
+            d.blk0 = (int32_t)blk; d.type = j.type;
+            if (!fmt_ingest(j.type) || j.n == 0) continue;
+            const bool il = j.inter && Cin == 2;
+            const bool two = Cin == 2 && !il && o.src[1] != o.src[0];
+            const size_t pl = (j.n + 3) & ~(size_t)3;
+            d.src[0] = (const uint8_t*)o.src[0]; d.src[1] = two ? (const uint8_t*)o.src[1] : nullptr;
+            d.dst[0] = plane; d.dst[1] = (il || two) ? plane + pl : plane;
+            d.inter = il ? 1 : 0; d.narr = two ? 2 : 1; d.nelem = (int64_t)j.n * (il ? 2 : 1); d.tiles = ingest_tiles(j.type, d.nelem);
+            blk += d.tiles * d.narr;
+            o.f32 = 1; o.stride = 1; o.src[0] = d.dst[0]; o.src[1] = d.dst[1];
+            plane += pl * (size_t)Cin;
+        }
+        if (blk > 0x7fffffff) { set_err("too many samples in one call"); return false; }
+        P.ingest_tiles = (int)blk;
+        if (!rt::h2d(ws.ingest_desc.p, id.data(), (size_t)S * sizeof(IngestDesc), st)) return false;
+        P.dING = (const IngestDesc*)ws.ingest_desc.p;
     }
     // All descriptors travel in ONE host-to-device copy (a small pageable copy costs ~10 us of host time each, and a 1-frame
     // call is only ~0.4 ms long): [StreamDesc x S | StreamIO x S | frame-slot map | granule-slot map], 16-byte aligned parts.

@@ -41,6 +41,7 @@ struct WorkSet {
     DevBuf pcm, peaks, loud, eb_l, mask_idx, eb_s, ecb_s, att_raw, uselong, ul_tmp, last_attack, tent, prev_short, blocktype,
         ath_adjust, ath_limit, E, sb, xr, side, l3, seed, seed_flag, nflagged, slow_list, frame_bytes, desc, in16, rejected, out8, prof, fht, hpf, tot_ener, reval, att_clean, nb1, nb2, fr, out_bytes, vdig, small;
     DevBuf crc_desc, crc_part, crc_out;     // { infoTag } streams only (g_out_crc): per-stream descriptors, span remainders, results
+    DevBuf ingest, ingest_desc;             // WAV sample types only (g_ingest): the Float32 planes of the call's new samples, per-stream descriptors
     PinBuf pin_in, pin_out;     // small host-buffer calls (run_batch): everything that travels in / out, staged once in pinned memory
     // last batch (for debug taps)
     Workspace lastW; int lastC = 0, lastCp = 0; bool have_last = false;

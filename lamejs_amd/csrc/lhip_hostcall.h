@@ -56,8 +56,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
         if (o > out_max) out_max = o;
     }
     const size_t stride = in_max, out_chunk = out_max + 64;
-    const int f32 = format & LHIP_PCM_F32;
-    const size_t bps = fmt_bps(f32);
+    const size_t bps = fmt_bps(fmt_type(format));
     const bool il = (format & LHIP_PCM_INTERLEAVED) && C == 2;
     // { infoTag } streams: every piece's music CRC stays on the device in the call's log (run_batch: crc_log) and the totals of the streams are brought up to date
     // once, after the last unit -- a failed call has then changed none of them
@@ -131,13 +130,12 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
             if (il) {                                      // interleaved two-channel input: one copy, read with stride 2
                 if (!rt::h2d(d_in + 2 * io * bps, pc.l, 2 * pc.n * bps, cs)) return fail(nullptr);
                 jobs[j] = Job{strs[pc.si], d_in + 2 * io * bps, nullptr, pc.n, d_out + oo, ocap, 0, 0, 0, 0};
-                jobs[j].inter = 1;
             } else {
                 if (!rt::h2d(d_in + io * bps, pc.l, pc.n * bps, cs)) return fail(nullptr);
                 if (C == 2 && !rt::h2d(d_in + (stride + io) * bps, pc.r ? pc.r : pc.l, pc.n * bps, cs)) return fail(nullptr);
                 jobs[j] = Job{strs[pc.si], d_in + io * bps, C == 2 ? d_in + (stride + io) * bps : nullptr, pc.n, d_out + oo, ocap, 0, 0, 0, 0};
             }
-            jobs[j].f32 = f32;
+            jobs[j].set_format(format);
             io += (pc.n + 63) & ~(size_t)63; oo += ocap;
         }
         if (!rt::event_record(ctx->ev_in[par], cs) || !rt::stream_wait_event(ks, ctx->ev_in[par])) return fail(nullptr);
@@ -197,7 +195,7 @@ static int64_t encode_host_chunked(lhip_stream* s, int format, const void* left,
     if ((size_t)batch_bytes(*s->ts, s->slot_lag, call_frames(s, nsamples)) > out_cap) { set_err("output buffer too small"); return LHIP_ERR_BUFFER_TOO_SMALL; }
     std::vector<std::vector<HostPiece>> units;
     const bool il = (format & LHIP_PCM_INTERLEAVED) && T.channels_in == 2;
-    const size_t step = fmt_bps(format & LHIP_PCM_F32) * (il ? 2 : 1);       // bytes from one sample position of the call to the next
+    const size_t step = fmt_bps(fmt_type(format)) * (il ? 2 : 1);       // bytes from one sample position of the call to the next
     {
         const size_t cap = cfg.cap * mul * spf;
         size_t p = 0, cur = cfg.first * mul * spf;
@@ -251,9 +249,31 @@ static bool scan_f32(const void* p, size_t count, float limit, size_t* where) {
 }
 // the host-pointer entries' check of one stream's input; on refusal lhip_last_error() names stream, channel, index and value
 // (channels: INPUT channels; limit: the stream's Tables::pcm_limit -- 131072, or less where its gains exceed 1)
+// the formats whose host calls are looked at first: the float types (an integer type cannot leave the contract)
+static inline bool fmt_scanned(int format) { const int t = fmt_type(format); return t == LHIP_PCM_F32 || (fmt_ingest(t) && ingest_is_float(t)); }
+// the WAV float types (k_ingest.h): the converted value decides, by the conversion the kernel makes
+static bool scan_ingest(int type, const void* p, size_t count, float limit, size_t* where) {
+    const size_t bps = fmt_bps(type);
+    for (size_t i = 0; i < count; i++) { unsigned bad = 0; (void)ingest_value<false>(type, (const uint8_t*)p + i * bps, limit, &bad); if (bad) { *where = i; return false; } }
+    return true;
+}
 static bool host_samples_ok(size_t stream_idx, int channels, float limit, int format, const void* left, const void* right, size_t n) {
-    if (!(format & LHIP_PCM_F32) || n == 0 || !left) return true;
+    if (!fmt_scanned(format) || n == 0 || !left) return true;
     const bool il = (format & LHIP_PCM_INTERLEAVED) && channels == 2;
+    if (fmt_type(format) != LHIP_PCM_F32) {
+        const int type = fmt_type(format);
+        size_t w = 0; int ch = 0; const void* bad = nullptr;
+        if (!scan_ingest(type, left, il ? 2 * n : n, limit, &w)) { bad = left; if (il) ch = (int)(w & 1); }
+        else if (!il && channels == 2 && right && right != left && !scan_ingest(type, right, n, limit, &w)) { bad = right; ch = 1; }
+        if (!bad) return true;
+        double v;
+        if (type == LHIP_PCM_F32N) { float x; memcpy(&x, (const uint8_t*)bad + 4 * w, 4); v = x; } else memcpy(&v, (const uint8_t*)bad + 8 * w, 8);
+        char txt[288];
+        snprintf(txt, sizeof txt, "%s sample outside the contract (finite, |%s| <= %g): stream %zu, channel %d, index %zu, value %g; nothing was consumed",
+                 type == LHIP_PCM_F32N ? "normalised Float32" : type == LHIP_PCM_F64N ? "normalised Float64" : "Float64", type == LHIP_PCM_F64 ? "x" : "32768 x", (double)limit, stream_idx, ch, il ? w / 2 : w, v);
+        set_err(txt);
+        return false;
+    }
     size_t w = 0;
     int ch = 0;
     const void* bad = nullptr;

@@ -267,6 +267,14 @@ __global__ __launch_bounds__(64) void g_out_crc(const CrcDesc* D, int nstreams, 
     const int s = crc_find_stream(D, nstreams, (int)blockIdx.x);
     kb_out_crc(D, s, (int)blockIdx.x - D[s].part0, threadIdx.x, partial);
 }
+// WAV sample types (k_ingest.h): one wave per tile of a stream's new samples, in front of the call's first reader; refused samples of the float types are
+// counted where g_count_rejected counts those of Float32 calls
+__global__ __launch_bounds__(64) void g_ingest(const IngestDesc* D, int nstreams, float limit, unsigned long long* ctr) {
+    __shared__ __attribute__((aligned(16))) uint8_t L[ING_WINDOW];
+    const int s = ingest_find_stream(D, nstreams, (int)blockIdx.x);
+    const unsigned bad = kb_ingest(D, s, (int64_t)blockIdx.x - D[s].blk0, threadIdx.x, L, limit);
+    if (ctr && bad && threadIdx.x == 0) atomicAdd(ctr, (unsigned long long)bad);
+}
 __global__ __launch_bounds__(64) void g_out_crc_fold(const CrcDesc* D, const uint32_t* partial, uint32_t* out) { kb_crc_fold(D, blockIdx.x, threadIdx.x, partial, out); }
 #ifndef LHIP_FRAME_PIPE
 #define LHIP_FRAME_PIPE 1      /* 0: the Huffman counts of the outer loop on the searching wave itself (A/B builds) */
@@ -349,8 +357,8 @@ template <int RESV> __global__ __launch_bounds__(64 * FR_WAVES) void g_frame(QAr
 #endif
 }
 // optional per-kernel timing with HIP events on the launch stream (bench.py roofline accounting)
-enum { KT_LOAD, KT_PREP, KT_PSYA, KT_SCAN, KT_PSYB, KT_POLY, KT_MDCT, KT_QUANT, KT_VALIDATE, KT_REPAIR, KT_BITS, KT_SAVE, KT_COUNT, KT_OUT_CRC, KT_N };
-static const char* const g_kt_names[KT_N] = {"load", "prep", "psyA", "scan", "psyB", "polyphase", "mdct", "quant", "validate", "repair", "bits", "save", "count_rejected", "out_crc"};
+enum { KT_LOAD, KT_PREP, KT_PSYA, KT_SCAN, KT_PSYB, KT_POLY, KT_MDCT, KT_QUANT, KT_VALIDATE, KT_REPAIR, KT_BITS, KT_SAVE, KT_COUNT, KT_OUT_CRC, KT_INGEST, KT_N };
+static const char* const g_kt_names[KT_N] = {"load", "prep", "psyA", "scan", "psyB", "polyphase", "mdct", "quant", "validate", "repair", "bits", "save", "count_rejected", "out_crc", "ingest"};
 // The switch is process-wide (bench.py turns it on for one extra, untimed step); the events of a batch belong to the calling
 // thread (a batch runs entirely inside one run_batch call), the accumulators are shared by all devices and guarded by g_kt_mu.
 static std::atomic<bool> g_kt_on{false};

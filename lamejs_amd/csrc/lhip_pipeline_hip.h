@@ -24,8 +24,13 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
         int64_t nb = (in_total + 255) / 256;
         if (nb > 2048) nb = 2048;
         if (nb < 1) nb = 1;
-        LAUNCHB(KT_COUNT, g_count_rejected, (int)nb, 256, st, dIO, S, T.channels_in, T.pcm_limit, (unsigned long long*)ws.rejected.p);
+        if (P.count_f32) LAUNCHB(KT_COUNT, g_count_rejected, (int)nb, 256, st, dIO, S, T.channels_in, T.pcm_limit, (unsigned long long*)ws.rejected.p);
         g_rej_pending = ctx;
+    }
+    // WAV sample types: the call's new samples become Float32 planes (dIO points at them) before anything reads them; the float types are cleaned and counted here
+    if (P.ingest_tiles > 0) {
+        P.paths |= LHIP_PATH_INGEST;
+        LAUNCH(KT_INGEST, g_ingest, P.ingest_tiles, st, P.dING, S, T.pcm_limit, P.count_rej ? (unsigned long long*)ws.rejected.p : (unsigned long long*)nullptr);
     }
     if (use_frame) {
         QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;

@@ -26,7 +26,14 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     const StreamDesc* dSD = P.dSD; const StreamIO* dIO = P.dIO;
     const int S = P.S, C = T.channels_out, ngs = P.ngs, nfs = P.nfs, nfr = P.nfr; const bool resv = P.resv, use_frame = P.use_frame;
     int64_t& repaired = P.repaired; int64_t& iters = P.iters;
-    if (P.count_rej) g_rejected = (int64_t)kb_count_rejected(dIO, S, T.channels_in, T.pcm_limit, 0, 1);
+    if (P.count_f32) g_rejected = (int64_t)kb_count_rejected(dIO, S, T.channels_in, T.pcm_limit, 0, 1);
+    if (P.ingest_tiles > 0) {       // g_ingest, workgroup by workgroup
+        P.paths |= LHIP_PATH_INGEST;
+        alignas(16) static thread_local uint8_t LI[ING_WINDOW];
+        unsigned long long bad = 0;
+        for (int b = 0; b < P.ingest_tiles; b++) { const int s = ingest_find_stream(P.dING, S, b); WAVE_RUN(const unsigned r = kb_ingest(P.dING, s, (int64_t)b - P.dING[s].blk0, lane_, LI, T.pcm_limit); if (lane_ == 0) bad += r); }
+        if (P.count_rej) g_rejected += (int64_t)bad;
+    }
     // (thread_local: with LHIP_HOSTSIM_DEVICES > 1 host threads batch on different contexts at the same time)
     static thread_local PsyALds LA; static thread_local PsyBLds4 LB; static thread_local MdctLds LM; static thread_local PolyLds LP; static thread_local QuantLds LQ; static thread_local BitsLds LBi; static thread_local QuantTabs QT;
     q_load_tabs(T, QT, 0, 1);

@@ -132,7 +132,10 @@ static int64_t encode_fmt(lhip_stream* s, int fmt, const void* dl, const void* d
     return fmt == LHIP_PCM_S16 ? p_encode(s, (const int16_t*)dl, (const int16_t*)dr, nl, out, cap) : p_encode_pcm(s, fmt, dl, dr, nl, out, cap);
 }
 /* -4 because a Float32 sample was refused (the library's text says so) -- every other -4 is swallowed into an empty array, as for Int16 input */
-static int refused_sample(int64_t rc, int fmt) { return rc == -4 && (fmt & LHIP_PCM_F32) && strstr(p_last_error(), "Float32 sample") != NULL; }
+static int fmt_float(int fmt) { const int t = fmt & ~LHIP_PCM_INTERLEAVED; return t == LHIP_PCM_F32 || t >= LHIP_PCM_F32N; }
+static int refused_sample(int64_t rc, int fmt) { return rc == -4 && fmt_float(fmt) && strstr(p_last_error(), "sample outside the contract") != NULL; }
+/* bytes per sample of a sample type (include/lamejs_hip.h), 0: not a type */
+static size_t type_bytes(int t) { return t == LHIP_PCM_S16 ? 2 : t == LHIP_PCM_F32 || t == LHIP_PCM_S32 || t == LHIP_PCM_F32N ? 4 : t == LHIP_PCM_U8 ? 1 : t == LHIP_PCM_S24 ? 3 : t == LHIP_PCM_F64N || t == LHIP_PCM_F64 ? 8 : 0; }
 static int pcm_type(napi_typedarray_type tt) { return tt == napi_int16_array ? LHIP_PCM_S16 : tt == napi_float32_array ? LHIP_PCM_F32 : -1; }
 static napi_value encode_into_new_array(napi_env env, lhip_stream* s, int fmt, const void* dl, const void* dr, size_t nl) {
     static uint8_t none[16];
@@ -187,6 +190,25 @@ static napi_value js_encode(napi_env env, napi_callback_info info) {
     return encode_into_new_array(env, s, fmt, dl, dr, nl);
 }
 
+/* encodePcm(handle, bytes, type, channels, interleaved): `bytes` a Uint8Array of samples of the sample type `type` (LHIP_PCM_*) as a WAV file stores them --
+ * interleaved, or the left plane followed by the right one.  The bytes travel as they are; the library converts them (lhip_encode_pcm). */
+static napi_value js_encode_pcm(napi_env env, napi_callback_info info) {
+    size_t argc = 5; napi_value argv[5];
+    napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
+    lhip_stream* s = NULL;
+    if (argc < 5 || napi_get_value_external(env, argv[0], (void**)&s) != napi_ok || !s) { napi_throw_type_error(env, NULL, "first argument must be a stream handle"); return NULL; }
+    napi_typedarray_type tt; size_t nb = 0; void* d = NULL;
+    if (napi_get_typedarray_info(env, argv[1], &tt, &nb, &d, NULL, NULL) != napi_ok || tt != napi_uint8_array) { napi_throw_type_error(env, NULL, "bytes must be a Uint8Array"); return NULL; }
+    int32_t type = -1, ch = 0; bool inter = true;
+    napi_get_value_int32(env, argv[2], &type); napi_get_value_int32(env, argv[3], &ch); napi_get_value_bool(env, argv[4], &inter);
+    const size_t bps = type_bytes(type);
+    if (!bps || (ch != 1 && ch != 2)) { napi_throw_type_error(env, NULL, "unknown sample type or channel count"); return NULL; }
+    if (nb % (bps * (size_t)ch)) { napi_throw_type_error(env, NULL, "the byte length must be a whole number of sample frames"); return NULL; }
+    const size_t n = nb / (bps * (size_t)ch);
+    if (ch == 2 && !inter) return encode_into_new_array(env, s, type, d, (const uint8_t*)d + n * bps, n);
+    return encode_into_new_array(env, s, type | (ch == 2 ? LHIP_PCM_INTERLEAVED : 0), d, NULL, n);
+}
+
 static napi_value js_flush(napi_env env, napi_callback_info info) {
     size_t argc = 1; napi_value argv[1];
     napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
@@ -205,11 +227,14 @@ static napi_value js_flush(napi_env env, napi_callback_info info) {
  * call must share one configuration and device (the library checks); a failed call throws (there is no reference behaviour to
  * mirror for it), a stream without completed frames gets an empty array. */
 static napi_value batch_common(napi_env env, napi_callback_info info, int is_flush) {
-    size_t argc = 4; napi_value argv[4];
+    size_t argc = 5; napi_value argv[5];
     napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
     uint32_t n = 0;
     int fmt = -1; int32_t inter = 0;         /* encodeBatch: the arrays' common type; 4th argument > 0: that many channels interleaved in lefts[i] */
+    int32_t raw = -1;                        /* 5th argument >= 0: the arrays are Uint8Arrays of samples of this sample type (LHIP_PCM_*) */
     if (!is_flush && argc > 3) { napi_valuetype v3; napi_typeof(env, argv[3], &v3); if (v3 == napi_number) napi_get_value_int32(env, argv[3], &inter); }
+    if (!is_flush && argc > 4) { napi_valuetype v4; napi_typeof(env, argv[4], &v4); if (v4 == napi_number) napi_get_value_int32(env, argv[4], &raw); }
+    if (raw >= 0 && !type_bytes(raw)) { napi_throw_type_error(env, NULL, "unknown sample type"); return NULL; }
     if (argc < 1 || napi_get_array_length(env, argv[0], &n) != napi_ok) { napi_throw_type_error(env, NULL, "handles must be an array"); return NULL; }
     napi_value result; napi_create_array_with_length(env, n, &result);
     if (n == 0) return result;
@@ -232,8 +257,13 @@ static napi_value batch_common(napi_env env, napi_callback_info info, int is_flu
         if (!is_flush) {
             napi_value a; napi_typedarray_type tt; void* d = NULL;
             napi_get_element(env, argv[1], i, &a);
+            if (raw >= 0) {
+                if (napi_get_typedarray_info(env, a, &tt, &ns[i], &d, NULL, NULL) != napi_ok || tt != napi_uint8_array || ns[i] % type_bytes(raw)) { err = "lefts must hold Uint8Arrays of whole samples"; break; }
+                ns[i] /= type_bytes(raw); fmt = raw;
+            } else {
             if (napi_get_typedarray_info(env, a, &tt, &ns[i], &d, NULL, NULL) != napi_ok || pcm_type(tt) < 0 || (fmt >= 0 && pcm_type(tt) != fmt)) { err = "lefts must hold Int16Arrays, or Float32Arrays throughout"; break; }
             fmt = pcm_type(tt);
+            }
             L[i] = d;
             if (inter > 0) {
                 if (inter > 2 || ns[i] % (size_t)inter) { err = "interleaved samples: the length must be a multiple of the channel count"; break; }
@@ -242,7 +272,7 @@ static napi_value batch_common(napi_env env, napi_callback_info info, int is_flu
                 size_t nr = 0; void* dr = NULL; napi_valuetype vt;
                 napi_get_element(env, argv[2], i, &a); napi_typeof(env, a, &vt);
                 if (vt != napi_null && vt != napi_undefined) {
-                    if (napi_get_typedarray_info(env, a, &tt, &nr, &dr, NULL, NULL) != napi_ok || pcm_type(tt) != fmt || nr != ns[i]) { err = "rights must hold arrays of their lefts' type and length"; break; }
+                    if (napi_get_typedarray_info(env, a, &tt, &nr, &dr, NULL, NULL) != napi_ok || (raw >= 0 ? (tt != napi_uint8_array || nr != ns[i] * type_bytes(raw)) : (pcm_type(tt) != fmt || nr != ns[i]))) { err = "rights must hold arrays of their lefts' type and length"; break; }
                     R[i] = dr;
                 }
             }
@@ -267,7 +297,7 @@ static napi_value batch_common(napi_env env, napi_callback_info info, int is_flu
         const int rc = is_flush ? p_flush_batch(hs, n, outs, caps, wr)
                      : f == LHIP_PCM_S16 ? p_encode_batch(hs, n, (const int16_t* const*)L, (const int16_t* const*)R, ns, outs, caps, wr)
                                          : p_encode_batch_pcm(hs, n, f, L, R, ns, outs, caps, wr);
-        if (rc != 0) { err = p_last_error(); range_err = !is_flush && (f & LHIP_PCM_F32) && rc == -4 && strstr(err, "Float32 sample") != NULL; }
+        if (rc != 0) { err = p_last_error(); range_err = !is_flush && fmt_float(f) && rc == -4 && strstr(err, "sample outside the contract") != NULL; }
     }
     if (!err) for (uint32_t i = 0; i < n; i++) {
         napi_value ta;
@@ -375,7 +405,7 @@ static napi_value js_flush_batch(napi_env env, napi_callback_info info) { return
 static napi_value init(napi_env env, napi_value exports) {
     napi_property_descriptor d[] = {
         {"deviceCount", 0, js_device_count, 0, 0, 0, napi_default, 0}, {"create", 0, js_create, 0, 0, 0, napi_default, 0},
-        {"encode", 0, js_encode, 0, 0, 0, napi_default, 0}, {"flush", 0, js_flush, 0, 0, 0, napi_default, 0},
+        {"encode", 0, js_encode, 0, 0, 0, napi_default, 0}, {"flush", 0, js_flush, 0, 0, 0, napi_default, 0}, {"encodePcm", 0, js_encode_pcm, 0, 0, 0, napi_default, 0},
         {"encodeBatch", 0, js_encode_batch, 0, 0, 0, napi_default, 0}, {"flushBatch", 0, js_flush_batch, 0, 0, 0, napi_default, 0},
         {"setDevices", 0, js_set_devices, 0, 0, 0, napi_default, 0},
         {"seekTailSamples", 0, js_seek_tail, 0, 0, 0, napi_default, 0}, {"callLimit", 0, js_call_limit, 0, 0, 0, napi_default, 0}, {"seek", 0, js_seek, 0, 0, 0, napi_default, 0},

@@ -87,6 +87,40 @@ function checkF32(a, what) {
         if (!(Math.abs(a[i]) <= PCM_LIMIT)) throw new RangeError('lamejs_amd: Float32 sample outside the contract (finite, |x| <= 131072): ' + what + ' index ' + i + ', value ' + a[i] + '; nothing was consumed');
 }
 
+/* Sample types a WAV file stores (include/lamejs_hip.h: LHIP_PCM_*), by the names encodePcm() and encodeBatch(..., { format }) take.  'f32' and 'f64'
+ * are the NORMALISED types: floats in [-1, 1], full scale = 32768. */
+const PCM_TYPES = { u8: [4, 1], s16: [0, 2], s24: [8, 3], s32: [12, 4], f32: [16, 4], f64: [20, 8] };
+function pcmType(format) {
+    const t = PCM_TYPES[format];
+    if (!t) throw new TypeError("lamejs_amd: format must be one of 'u8', 's16', 's24', 's32', 'f32', 'f64'");
+    return t;
+}
+function asBytes(b) {
+    if (b instanceof Uint8Array) return b;
+    if (b instanceof ArrayBuffer) return new Uint8Array(b);
+    if (ArrayBuffer.isView(b)) return new Uint8Array(b.buffer, b.byteOffset, b.byteLength);
+    throw new TypeError('lamejs_amd: bytes must be a Uint8Array, a Buffer, an ArrayBuffer or a view of one');
+}
+/* the value the encoder sees for element e of `bytes` (the header's table): what { pendingFrames } holds back of such input, as Float32 */
+function pcmValue(dv, format, e) {
+    switch (format) {
+        case 'u8': return (dv.getUint8(e) - 128) * 256;
+        case 's16': return dv.getInt16(2 * e, true);
+        case 's24': return ((dv.getUint8(3 * e) | (dv.getUint8(3 * e + 1) << 8) | (dv.getInt8(3 * e + 2) << 16))) / 256;
+        case 's32': return dv.getInt32(4 * e, true) / 65536;
+        case 'f32': return dv.getFloat32(4 * e, true) * 32768;
+        default: return dv.getFloat64(8 * e, true) * 32768;
+    }
+}
+/* the float types' contract as the library applies it: the value (a double: compared BEFORE it is rounded to Float32) must be finite and within the limit */
+function checkPcm(dv, format, count, where) {
+    if (format != 'f32' && format != 'f64') return;
+    for (let e = 0; e < count; e++) {
+        const v = pcmValue(dv, format, e);
+        if (!(Math.abs(v) <= PCM_LIMIT)) throw new RangeError('lamejs_amd: sample outside the contract (finite, |32768 x| <= 131072): ' + where(e) + ', value ' + v / 32768 + '; nothing was consumed');
+    }
+}
+
 function Mp3Encoder(channels, samplerate, kbps, opts) {
     if (arguments.length != 3 && !(arguments.length == 4 && opts !== null && typeof opts == 'object')) {
         opts = undefined;
@@ -151,6 +185,24 @@ function Mp3Encoder(channels, samplerate, kbps, opts) {
         for (let i = 0; i < n; i++) { l[i] = samples[2 * i]; r[i] = samples[2 * i + 1]; }
         return this.encodeBuffer(l, r);
     };
+    /* Extension: PCM as a WAV file stores it -- encodePcm(bytes, format[, { interleaved = true }]).  format: 'u8', 's16', 's24', 's32', 'f32', 'f64' (the two
+     * float names: samples in [-1, 1]); interleaved (L R L R ..., as in the file) or the left plane followed by the right one.  The bytes travel as they
+     * are and a kernel converts them; only a call small enough for one pinned block (a few frames) is converted by the host while it fills that block, and a
+     * call of a float type is scanned by the library first.  A float sample that is not finite or lies beyond +-4 is a RangeError and
+     * consumes nothing.  With { pendingFrames } the input is held back as the Float32 values it stands for. */
+    this.encodePcm = function (bytes, format, o) {
+        const [type, bps] = pcmType(format), u8 = asBytes(bytes), inter = !(o && o.interleaved === false);
+        if (u8.length % (bps * channels)) throw new TypeError('encodePcm: the byte length must be a whole number of sample frames');
+        if (!pendMax) return native.encodePcm(handle, u8, type, channels, inter);
+        const n = u8.length / (bps * channels), dv = new DataView(u8.buffer, u8.byteOffset, u8.byteLength);
+        const l = new Float32Array(n), r = channels == 2 ? new Float32Array(n) : null;
+        checkPcm(dv, format, u8.length / bps, (e) => 'channel ' + (r ? (inter ? e & 1 : (e < n ? 0 : 1)) : 0) + ', index ' + (r && inter ? e >> 1 : e % n));      /* as the library does: before the rounding */
+        for (let i = 0; i < n; i++) {
+            l[i] = pcmValue(dv, format, r && inter ? 2 * i : i);
+            if (r) r[i] = pcmValue(dv, format, inter ? 2 * i + 1 : n + i);
+        }
+        return this.encodeBuffer(l, r);
+    };
     this.flush = function () {
         if (!pendMax || pendN == 0) return native.flush(handle);
         const a = drain(), b = native.flush(handle);
@@ -193,6 +245,38 @@ WavHeader.readHeader = function (dataView) {
     w.dataOffset = pos + 8;
     return w;
 };
+/* Extension: what encodePcm() needs to know of a WAV file -- { format, channels, sampleRate, dataOffset, dataLen }, format one of encodePcm's names.
+ * `fmt ` chunks of 16, 18 and 40 bytes: PCM (1), IEEE float (3), and WAVE_FORMAT_EXTENSIBLE (0xFFFE) by the first two bytes of its sub-format;
+ * 8, 16, 24 and 32 bits for PCM, 32 and 64 for float.  Anything else throws. */
+WavHeader.readFormat = function (dataView) {
+    const tag = (o) => String.fromCharCode(dataView.getUint8(o), dataView.getUint8(o + 1), dataView.getUint8(o + 2), dataView.getUint8(o + 3));
+    if (dataView.byteLength < 28 || tag(0) != 'RIFF' || tag(8) != 'WAVE' || tag(12) != 'fmt ') throw new Error('readFormat: not a RIFF/WAVE file with a leading fmt chunk');
+    const fmtLen = dataView.getUint32(16, true);
+    if (fmtLen != 16 && fmtLen != 18 && fmtLen != 40) throw new Error('readFormat: fmt chunk of ' + fmtLen + ' bytes not supported');
+    let code = dataView.getUint16(20, true);
+    const channels = dataView.getUint16(22, true), sampleRate = dataView.getUint32(24, true), bits = dataView.getUint16(34, true);
+    if (code == 0xFFFE) {
+        if (fmtLen != 40 || dataView.getUint16(36, true) < 22) throw new Error('readFormat: WAVE_FORMAT_EXTENSIBLE needs a fmt chunk of 40 bytes');
+        code = dataView.getUint16(44, true);              /* the sub-format GUID starts with the format code */
+        const valid = dataView.getUint16(38, true);
+        if (valid != 0 && valid != bits) throw new Error('readFormat: ' + valid + ' valid bits in a container of ' + bits + ' not supported');
+    }
+    const format = code == 1 ? { 8: 'u8', 16: 's16', 24: 's24', 32: 's32' }[bits] : code == 3 ? { 32: 'f32', 64: 'f64' }[bits] : undefined;
+    if (!format) throw new Error('readFormat: format code ' + code + ' with ' + bits + ' bits per sample not supported');
+    if (channels != 1 && channels != 2) throw new Error('readFormat: ' + channels + ' channels not supported');
+    if (dataView.getUint16(32, true) != channels * PCM_TYPES[format][1]) throw new Error('readFormat: block align does not match the sample type (padded containers are not supported)');
+    let pos = 20 + fmtLen;
+    for (;;) {
+        if (pos + 8 > dataView.byteLength) throw new Error('readFormat: no data chunk');
+        const len = dataView.getUint32(pos + 4, true);
+        if (tag(pos) == 'data') {
+            /* a length beyond the view (0xFFFFFFFF in a streamed file, a truncated file): what is there, in whole sample frames */
+            const frame = channels * PCM_TYPES[format][1], have = dataView.byteLength - (pos + 8);
+            return { format: format, channels: channels, sampleRate: sampleRate, dataOffset: pos + 8, dataLen: len <= have ? len : have - have % frame };
+        }
+        pos += 8 + len + (len & 1);
+    }
+};
 
 module.exports.Mp3Encoder = Mp3Encoder;
 module.exports.WavHeader = WavHeader;
@@ -207,6 +291,8 @@ module.exports.deviceCount = function () { return loadAddon().deviceCount(); };
  *                                         bytes each encoder's own encodeBuffer() would have returned.  Int16 if every array is an
  *                                         Int16Array, otherwise the whole batch as Float32 (still one launch); interleaved: lefts[i]
  *                                         holds channels * n samples (L R L R ...), rights is ignored
+ *                                         { format: 'u8' | 's16' | 's24' | 's32' | 'f32' | 'f64' }: the arrays are Uint8Arrays of samples
+ *                                         of that type (see Mp3Encoder.encodePcm); a refused float sample is a RangeError
  *   flushBatch(encoders)                  likewise for flush()
  *   setDevices(mask)                      let the library deal new encoders round-robin over the GPUs named by the bit mask
  * The encoders of one call must share the channel count and the device; encoders of one configuration share a launch, other configurations and
@@ -227,6 +313,17 @@ module.exports.encodeBatch = function (encoders, lefts, rights, opts) {
     const channels = encoders.length > 0 ? encoders[0]._lhip.channels : 1;
     const inter = !!(opts && opts.interleaved);
     const nl = lefts.length;
+    if (opts && opts.format !== undefined) {          /* { format }: Uint8Arrays of samples as a WAV file stores them (Mp3Encoder.encodePcm); they travel as they are */
+        const [type, bps] = pcmType(opts.format);
+        /* a refused sample consumes nothing, held-back input included: where something is held back, the float types are looked at before it is encoded */
+        if ((opts.format == 'f32' || opts.format == 'f64') && encoders.some((e) => e._lhip.pending() > 0))
+            lefts.concat(channels == 2 && rights && !inter ? rights : []).forEach((b, i) => {
+                const u8 = asBytes(b), dv = new DataView(u8.buffer, u8.byteOffset, u8.byteLength);
+                checkPcm(dv, opts.format, u8.length / bps, (e) => 'array ' + i + ', element ' + e);
+            });
+        const heads = drainPending(encoders);
+        return prepend(heads, loadAddon().encodeBatch(hs, lefts.map(asBytes), channels == 2 && rights && !inter ? rights.map(asBytes) : null, inter ? channels : 0, type));
+    }
     const all = sameType(lefts.concat(channels == 2 && rights && !inter ? rights : []).map((a) => (isPcm(a) ? a : Float32Array.from(a))));
     const L = all.slice(0, nl), R = all.length > nl ? all.slice(nl) : null;
     /* checked BEFORE anything held back by { pendingFrames } is encoded: a refused sample consumes nothing, held-back input included */
