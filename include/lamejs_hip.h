@@ -277,6 +277,8 @@ void lhip_last_batch_stats(int64_t* frames, int64_t* repaired_frames, int64_t* r
 /* (and INGEST 0x4000: samples of a LHIP_PCM_U8 .. LHIP_PCM_F64 call were turned into Float32 planes by the kernel g_ingest; such a call without this bit was a
  *  SMALL_CALL, converted by the host) */
 #define LHIP_PATH_INGEST (1u << 14)
+/* (and GAIN 0x8000: the batch held { replayGain } streams: the kernels g_gain_stage and g_gain ran behind it; never set for a stream without the option) */
+#define LHIP_PATH_GAIN (1u << 15)
 int lhip_debug_last_paths(uint32_t* mask);
 
 /* Info tag (extension; see above).  What a stream built with { infoTag } has put out so far, and the finished tag frame. */
@@ -300,6 +302,25 @@ int64_t lhip_info_tag(lhip_stream* s, uint8_t* out, size_t cap);
 size_t lhip_debug_crc_span(void);
 int lhip_debug_crc16(const void* bytes, size_t n, size_t misalign, uint32_t* crc);
 int lhip_debug_info_toc(const int64_t* frames, size_t ncalls, int kbps, uint8_t* toc);
+/* ReplayGain (extension): a stream whose table blob was built with { replayGain } analyses the Float32 samples its encoder consumes -- behind the input gains,
+ * the downmix and the resampler; every call's new samples, the zeros of the flush included; the left and right channel of a joint-stereo stream -- on the
+ * device, by the published ReplayGain method as the reference's GainAnalysis.js states it: per output channel a 10th-order "Yule" filter and a 2nd-order
+ * Butterworth high-pass (f64 arithmetic, outputs stored as Float32), the energy over windows of ceil(out_samplerate / 20) samples, one count per window in a
+ * histogram of 0.01 dB steps; at the end the bin below which 95 % of the windows lie gives the track gain 64.82 dB - bin / 100.
+ * The result is a pure function of the sample stream: any cut into calls, encode_batch and the device entries give the same histogram.  A window's energy is
+ * computed from a recursion restarted a fixed number of samples in front of it, so it is the reference's bit for bit for the first windows of a stream and
+ * within rounding noise (far below one histogram step) elsewhere -- INTEGRATION.md "ReplayGain".  Nothing is read back per call: an asynchronous device call
+ * stays asynchronous.  With { infoTag } the tag frame's radio ReplayGain field carries the value (peak amplitude and the audiophile field stay zero).
+ * lhip_create returns -3 for a { replayGain } blob that resamples by a non-integer ratio.  State blobs do not carry the analysis.
+ * lhip_replay_gain synchronises the stream's device context and returns 0 with *tenth_db = the track gain in tenths of a dB (RadioGain of the reference),
+ * *windows = complete windows analysed and *samples = samples analysed; 1 with *tenth_db = 0 when no window is complete yet (the reference asserts there);
+ * -4 with a message for a stream without the option or one that was moved with lhip_seek / lhip_state_set. */
+int lhip_replay_gain(lhip_stream* s, int32_t* tenth_db, int64_t* windows, int64_t* samples);
+/* Test hooks.  lhip_debug_gain_histogram: the stream's 12000 histogram counts (synchronises; same refusals).  lhip_debug_gain_windows: THE KERNELS g_gain_stage and
+ * g_gain (in the simulation libraries: their bodies) over n samples per channel (l; r for two channels) as one call of a fresh stream at output rate fs: bins and
+ * energies receive floor(n / window) entries, each window's histogram bin and its lsum + rsum.  Returns that number of windows, or < 0. */
+int lhip_debug_gain_histogram(lhip_stream* s, uint32_t* A);
+int lhip_debug_gain_windows(int fs, int channels, const float* l, const float* r, size_t n, int32_t* bins, double* energies);
 /* Test hook.  lhip_debug_ingest: THE KERNEL g_ingest (in the simulation libraries: its body) over the caller's samples in `format` (one of the LHIP_PCM_U8 ..
  * LHIP_PCM_F64 types, optionally INTERLEAVED), placed misalign (0 .. 15) bytes past a 16-byte boundary of a device buffer of exactly that size: channels (1 or
  * 2) * nsamples elements -- interleaved, or the left plane followed by the right one.  left / right (right: two channels only) receive nsamples floats each,

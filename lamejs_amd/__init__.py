@@ -22,7 +22,7 @@ _PKG = Path(__file__).resolve().parent
 _LIB_PATH = _PKG / "lib" / "liblamejs_hip.so"
 _TABLE_DIR = _PKG / "tables"
 
-__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED", "PATH_NAMES", "PATH_NAMES_ALL", "PATH_BITS", "last_batch_paths", "StreamInfo",
+__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED", "PATH_NAMES", "PATH_NAMES_ALL", "PATH_BITS", "PATH_BITS_ALL", "last_batch_paths", "StreamInfo",
            "PCM_U8", "PCM_S24", "PCM_S32", "PCM_F32N", "PCM_F64N", "PCM_F64", "PCM_BYTES"]
 
 # launch paths of a batch (include/lamejs_hip.h: LHIP_PATH_*), in bit order
@@ -32,6 +32,9 @@ PATH_NAMES = ("FRAME", "FRAME_RESV", "SEPARATE", "PREP", "PSY4", "QUANT_PAIR", "
 # g_out_crc, not from the host) and INGEST (samples of a WAV sample type were turned into Float32 planes by the kernel g_ingest, not by the host)
 PATH_BITS = PATH_NAMES + ("OUT_CRC", "INGEST")
 PATH_NAMES_ALL = PATH_BITS[:14]      # (the names up to OUT_CRC, kept for callers that index it)
+# ... and GAIN: the batch held ``replay_gain`` streams and the kernels g_gain_stage / g_gain ran behind it.  (A tuple of its own: PATH_BITS is held at its
+# fifteen names by the suite, as PATH_NAMES is at thirteen.)
+PATH_BITS_ALL = PATH_BITS + ("GAIN",)
 
 
 def last_batch_paths(lib=None) -> frozenset:
@@ -41,9 +44,9 @@ def last_batch_paths(lib=None) -> frozenset:
     rc = lib.lhip_debug_last_paths(ctypes.byref(m))
     if rc != 0:
         raise LhipError(f"lhip_debug_last_paths failed ({rc}): {lib.lhip_last_error().decode()}")
-    if m.value >> len(PATH_BITS):
+    if m.value >> len(PATH_BITS_ALL):
         raise LhipError(f"lhip_debug_last_paths: unknown bits in {m.value:#x}")
-    return frozenset(n for i, n in enumerate(PATH_BITS) if m.value >> i & 1)
+    return frozenset(n for i, n in enumerate(PATH_BITS_ALL) if m.value >> i & 1)
 
 
 # sample formats of the *_pcm entries (include/lamejs_hip.h: LHIP_PCM_*): a sample type, optionally or-ed with PCM_INTERLEAVED
@@ -116,6 +119,9 @@ ABI = {
     "lhip_debug_crc16": (_int, [_ptr, _size, _size, ctypes.POINTER(ctypes.c_uint32)]),
     "lhip_debug_info_toc": (_int, [_ptr, _size, _int, _ptr]),
     "lhip_debug_ingest": (_int, [_int, _int, _ptr, _size, _size, _ptr, _ptr, _pi64]),
+    "lhip_replay_gain": (_int, [_ptr, _pi32, _pi64, _pi64]),
+    "lhip_debug_gain_histogram": (_int, [_ptr, _ptr]),
+    "lhip_debug_gain_windows": (_int, [_int, _int, _ptr, _ptr, _size, _ptr, _ptr]),
     "lhip_last_error": (ctypes.c_char_p, []),
     "lhip_version": (ctypes.c_char_p, []),
 }
@@ -175,7 +181,7 @@ def _gain_text(g) -> str:
 
 def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, reservoir: bool = False, fractional_resample: bool = False,
                 downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False, copyright: bool = False, original: bool = True,
-                private_bit: bool = False, emphasis: int = 0, info_tag: bool = False) -> bytes:
+                private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False) -> bytes:
     """The LHTB table blob for a configuration.
 
     Built by the host-side JavaScript ``lamejs_amd/js/tables.js`` (so every transcendental comes
@@ -191,8 +197,10 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     (``{ protect, copyright, original, privateBit, emphasis }`` of tables.js); at their defaults the blob is the bytes it always was.
     ``info_tag``: the stream starts with the placeholder of an Info/LAME tag frame and keeps the totals the tag reports (``{ infoTag }`` of
     tables.js: the tag's constants as named entries that exist only with the option); without it the blob is the bytes it always was.
+    ``replay_gain``: the stream analyses the samples it encodes for its ReplayGain track gain (``{ replayGain }`` of tables.js: one named entry that
+    exists only with the option); without it the blob is the bytes it always was.
     """
-    for name, v in (("protect", protect), ("copyright", copyright), ("original", original), ("private_bit", private_bit), ("info_tag", info_tag)):
+    for name, v in (("protect", protect), ("copyright", copyright), ("original", original), ("private_bit", private_bit), ("info_tag", info_tag), ("replay_gain", replay_gain)):
         if v not in (True, False, 0, 1):
             raise ValueError(f"{name} must be True or False")
     if isinstance(emphasis, bool) or emphasis not in (0, 1, 3):
@@ -206,6 +214,7 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     mix = (["downmix"] if downmix else []) + [f"{k}={_gain_text(v)}" for k, v in (("scale", scale), ("scaleLeft", scale_left), ("scaleRight", scale_right)) if v is not None]
     mix += (["protect"] if protect else []) + (["copyright"] if copyright else []) + ([] if original else ["original=0"]) + (["privateBit"] if private_bit else []) + ([f"emphasis={int(emphasis)}"] if emphasis else [])
     mix += ["infoTag"] if info_tag else []
+    mix += ["replayGain"] if replay_gain else []
     f = _TABLE_DIR / f"t_{channels}_{samplerate}_{kbps}{'_joint' if joint else ''}{'_resv' if reservoir else ''}{'_frac' if frac else ''}{''.join('_' + m.replace('=', '') for m in mix)}.bin"
     if not f.exists() or not blob_is_current(f.read_bytes()):      # a cached blob made by another version of its generator is stale
         _TABLE_DIR.mkdir(exist_ok=True)
@@ -260,7 +269,7 @@ class Mp3Encoder:
 
     def __init__(self, channels: int = 1, samplerate: int = 44100, kbps: int = 128, device: int = -1, lib=None, joint: bool = False, reservoir: bool = False,
                  fractional_resample: bool = False, downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False,
-                 copyright: bool = False, original: bool = True, private_bit: bool = False, emphasis: int = 0, info_tag: bool = False):
+                 copyright: bool = False, original: bool = True, private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False):
         """``joint`` (extension, not in the reference's wrapper): encode two channels in the reference's joint-stereo mode --
         per frame mid/side or left/right, as its encoder core decides when asked for MPEGMode.JOINT_STEREO.
         ``reservoir`` (extension): encode with the bit reservoir in use (the reference's wrapper disables it, index.js:108); the frames
@@ -278,12 +287,14 @@ class Mp3Encoder:
         ``emphasis`` (0, 1 or 3; 2 is reserved): the header bits of those names.  A value outside these raises ``ValueError``.
         ``info_tag`` (extension): the stream is a file -- its first call returns the placeholder of an Info/LAME tag frame in front of the audio
         (which is byte for byte the stream without the option), ``stream_info()`` reports the totals, and after ``flush()``
-        ``info_tag_frame()`` returns the finished frame to be written over the placeholder at offset 0 (include/lamejs_hip.h, "Info tag")."""
+        ``info_tag_frame()`` returns the finished frame to be written over the placeholder at offset 0 (include/lamejs_hip.h, "Info tag").
+        ``replay_gain`` (extension): the samples the encoder consumes (behind gains, downmix and resampler) are analysed on the device as the reference
+        core's ReplayGain analysis does; ``replay_gain()`` reports the track gain, and with ``info_tag`` the tag's radio field carries it."""
         self._lib = lib or load_library()
         self.channels, self.samplerate, self.kbps = int(channels), int(samplerate), int(kbps)
         self._resv = bool(reservoir)
         blob = tables_blob(self.channels, self.samplerate, self.kbps, joint, reservoir, fractional_resample, downmix, scale, scale_left, scale_right,
-                           protect, copyright, original, private_bit, emphasis, info_tag)
+                           protect, copyright, original, private_bit, emphasis, info_tag, replay_gain)
         cfg = _Config(self.channels, self.samplerate, self.kbps, device)
         h = ctypes.c_void_p()
         buf = ctypes.create_string_buffer(blob, len(blob))
@@ -307,6 +318,15 @@ class Mp3Encoder:
         if n < 0:
             raise LhipError(f"lhip_info_tag failed ({n}): {self._lib.lhip_last_error().decode()}")
         return out[:n].tobytes()
+
+    def replay_gain(self):
+        """``replay_gain`` streams: ``(tenth_db, windows, samples)`` -- the track gain in tenths of a dB (``None`` while no window of
+        ``ceil(out_samplerate / 20)`` samples is complete), the complete windows and the samples analysed so far.  Waits for the stream's device."""
+        t, w, n = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64()
+        rc = self._lib.lhip_replay_gain(self._h, ctypes.byref(t), ctypes.byref(w), ctypes.byref(n))
+        if rc < 0:
+            raise LhipError(f"lhip_replay_gain failed ({rc}): {self._lib.lhip_last_error().decode()}")
+        return (t.value if rc == 0 else None), w.value, n.value
 
     def call_limit(self) -> int:
         """``fractional_resample`` streams: the ``encodeBuffer`` length that is accepted whatever calls came before (0: any length goes)."""

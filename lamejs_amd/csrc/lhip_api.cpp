@@ -19,6 +19,7 @@
 #include "k_bits.h"
 #include "k_crc.h"
 #include "k_ingest.h"
+#include "k_gain.h"
 
 #include <string>
 #include <vector>
@@ -45,6 +46,7 @@ using namespace lhip;
 #ifndef LHIP_HOSTSIM
 #include "lhip_kernels.h"
 #endif
+#include "lhip_gain.h"
 #include "lhip_infotag.h"
 #include "lhip_tables.h"
 #include "lhip_context.h"
@@ -225,6 +227,7 @@ int lhip_create(const lhip_config* cfg, const void* tables, size_t tables_bytes,
     std::unique_ptr<lhip_stream> s(new lhip_stream());
     s->ctx = ctx; s->ts = ts;
     if (ts->tag.on) s->tag.reset(new TagTotals());
+    if (ts->gain_on) { s->gain.reset(gain_create(ts->T.out_samplerate, ts->T.channels_out, ctx->stream)); if (!s->gain) return LHIP_ERR_INTERNAL; }
     s->slot_lag = ts->T.frac_SpF;
     // initial carried state (PsyModel.js:2566-2596 psymodel_init, Lame.js:168-171 lame_init_old)
     std::unique_ptr<StreamState> h(new StreamState());
@@ -535,6 +538,7 @@ int lhip_state_set(lhip_stream* s, const void* buf, size_t n) {
     if (!rt::set_device(ctx->device) || !rt::h2d(s->d_state, (const uint8_t*)buf + sizeof h, sizeof(StreamState), ctx->stream) || !rt::sync(ctx->stream)) return LHIP_ERR_INTERNAL;
     s->mf_size = h.mf_size; s->mf_samples_to_encode = h.mf_samples_to_encode; s->slot_lag = h.slot_lag; s->frame_num = h.frame_num; s->rs_n_in = h.rs_n_in;
     if (s->tag) s->tag->moved = true;          // (state blobs do not carry the tag's totals)
+    if (s->gain) s->gain->moved = true;        // (... nor the gain analysis' history and histogram)
     return 0;
 }
 size_t lhip_seek_tail_samples(const lhip_stream* s) {
@@ -578,6 +582,7 @@ int lhip_seek(lhip_stream* s, int64_t sample_pos, const int16_t* tail_left, cons
     const int64_t k = sample_pos / frame;                     // the stream has emitted k - 1 frames
     s->frame_num = k - 1;
     if (s->tag) s->tag->moved = true;
+    if (s->gain) s->gain->moved = true;
     s->rs_n_in = sample_pos;
     s->mf_size = ntail;
     s->mf_samples_to_encode = 576 + 1152 + frame;
@@ -718,7 +723,14 @@ int64_t lhip_info_tag(lhip_stream* s, uint8_t* out, size_t cap) {
     if (!s->tag->flushed) { set_err("lhip_info_tag: the stream has not been flushed (the tag reports the totals and the end padding of the complete stream)"); return LHIP_ERR_INTERNAL; }
     const size_t n = (size_t)s->ts->tag.size;
     if (!out || cap < n) { set_err("output buffer too small"); return LHIP_ERR_BUFFER_TOO_SMALL; }
-    tag_write(s->ts->T, s->ts->tag, *s->tag, out);
+    uint32_t radio = 0;
+    if (s->gain) {          // { replayGain }: the radio field, when at least one window is complete
+        int32_t tenth = 0; int64_t windows = 0, samples = 0;
+        const int rc = lhip_replay_gain(s, &tenth, &windows, &samples);
+        if (rc < 0) return rc;
+        if (rc == 0) radio = gain_tag_field(tenth);
+    }
+    tag_write(s->ts->T, s->ts->tag, *s->tag, out, radio);
     return (int64_t)n;
 }
 // Test hooks.  lhip_debug_crc_span: the bytes one workgroup of the CRC kernel covers.  lhip_debug_crc16: the kernel (in the simulations: its body) over a
@@ -821,6 +833,73 @@ int lhip_debug_ingest(int format, int channels, const void* bytes, size_t nsampl
 #endif
     rt::dfree(buf); rt::dfree(pl); rt::dfree(pr); rt::dfree(aux);
     return ok ? 0 : LHIP_ERR_INTERNAL;
+}
+// ---- ReplayGain (extension { replayGain }; k_gain.h, lhip_gain.h) ----
+static int gain_fetch(lhip_stream* s, const char* who, std::vector<uint32_t>& A, GainState& gs) {
+    if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    if (!s->gain) { set_err(std::string(who) + ": the stream was not created with the replayGain option"); return LHIP_ERR_INTERNAL; }
+    if (s->gain->moved) { set_err(std::string(who) + ": the stream was moved with lhip_seek or lhip_state_set (or a chunked call failed half way); state blobs do not carry the analysis' history and histogram"); return LHIP_ERR_INTERNAL; }
+    Context* ctx = s->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    A.assign(GAIN_BINS, 0u);
+    if (!rt::set_device(ctx->device) || !rt::d2h(&gs, s->gain->state(), sizeof gs, ctx->stream) || !rt::d2h(A.data(), s->gain->bins(), (size_t)GAIN_BINS * 4, ctx->stream) || !rt::sync(ctx->stream)) return LHIP_ERR_INTERNAL;
+    return 0;
+}
+int lhip_replay_gain(lhip_stream* s, int32_t* tenth_db, int64_t* windows, int64_t* samples) {
+    if (!tenth_db || !windows || !samples) { set_err("lhip_replay_gain: null argument"); return LHIP_ERR_INTERNAL; }
+    std::vector<uint32_t> A; GainState gs;
+    const int rc = gain_fetch(s, "lhip_replay_gain", A, gs);
+    if (rc < 0) return rc;
+    *samples = gs.samples;
+    return gain_result(A.data(), tenth_db, windows);
+}
+int lhip_debug_gain_histogram(lhip_stream* s, uint32_t* A) {
+    if (!A) { set_err("lhip_debug_gain_histogram: null argument"); return LHIP_ERR_INTERNAL; }
+    std::vector<uint32_t> v; GainState gs;
+    const int rc = gain_fetch(s, "lhip_debug_gain_histogram", v, gs);
+    if (rc < 0) return rc;
+    memcpy(A, v.data(), (size_t)GAIN_BINS * 4);
+    return 0;
+}
+// Test hook: the two kernels (in the simulations: their bodies) over n samples per channel as ONE call of a fresh stream at output rate fs; bins / energies
+// receive floor(n / window) entries: each window's histogram bin and lsum + rsum.
+int lhip_debug_gain_windows(int fs, int channels, const float* l, const float* r, size_t n, int32_t* bins, double* energies) {
+    const int ri = gain_rate_index(fs);
+    if (ri < 0 || (channels != 1 && channels != 2) || !l || (channels == 2 && !r) || n == 0 || n > 0x7fffffff || !bins || !energies) { set_err("lhip_debug_gain_windows: bad argument"); return LHIP_ERR_INTERNAL; }
+    if (rt::device_count() <= 0) { set_err("no HIP device available (this library has no CPU fallback)"); return LHIP_ERR_INTERNAL; }
+    const size_t nwin = n / (size_t)gain_window(ri);
+    std::unique_ptr<GainRec> g(gain_create(fs, channels, nullptr));
+    float* src = (float*)rt::dmalloc((size_t)channels * n * 4);                // exactly the samples: a read past them is outside the block
+    int32_t* dB = (int32_t*)rt::dmalloc(nwin * 4 + 4); double* dE = (double*)rt::dmalloc(nwin * 8 + 8);
+    StreamIO* dIO = (StreamIO*)rt::dmalloc(sizeof(StreamIO)); StreamDesc* dSD = (StreamDesc*)rt::dmalloc(sizeof(StreamDesc)); GainDesc* dGD = (GainDesc*)rt::dmalloc(sizeof(GainDesc));
+    GainPlan P; GainRec* rec = g.get(); const int64_t nn = (int64_t)n;
+    bool ok = g && src && dB && dE && dIO && dSD && dGD && gain_plan(&rec, &nn, 1, P, dB, dE);
+    float* rows = ok ? (float*)rt::dmalloc(P.row_floats * 4) : nullptr;       // exactly the rows
+    ok = ok && rows;
+    if (ok) {
+        gain_bind_rows(P, rows);
+        Tables T; memset(&T, 0, sizeof T);                                    // a stream without gains, mix or resampler: the samples are used as given
+        T.channels_out = channels; T.channels_in = channels; T.rs_ratio = 1; T.pcm_limit = PCM_F32_LIMIT; T.scale = 1.0;
+        Workspace W; memset(&W, 0, sizeof W);
+        StreamDesc sd; memset(&sd, 0, sizeof sd);
+        StreamIO io; memset(&io, 0, sizeof io);
+        io.src[0] = src; io.src[1] = channels == 2 ? src + n : src; io.f32 = 1; io.stride = 1; io.n_new = (int32_t)n; io.n_in = (int32_t)n;
+        ok = rt::h2d(src, l, n * 4, nullptr) && (channels == 1 || rt::h2d(src + n, r, n * 4, nullptr)) && rt::h2d(dIO, &io, sizeof io, nullptr) && rt::h2d(dSD, &sd, sizeof sd, nullptr) &&
+             rt::h2d(dGD, P.d.data(), sizeof(GainDesc), nullptr) && rt::sync(nullptr);
+#ifndef LHIP_HOSTSIM
+        if (ok) {
+            hipLaunchKernelGGL(g_gain_stage, dim3(P.stage_blocks), dim3(GAIN_STAGE_NT), 0, 0, T, W, (const StreamDesc*)dSD, (const StreamIO*)dIO, (const GainDesc*)dGD, 1);
+            if (P.waves > 0) { if (channels == 2) hipLaunchKernelGGL(g_gain<2>, dim3(P.waves), dim3(64), 0, 0, (const GainDesc*)dGD, 1); else hipLaunchKernelGGL(g_gain<1>, dim3(P.waves), dim3(64), 0, 0, (const GainDesc*)dGD, 1); }
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { set_err(std::string("g_gain: ") + hipGetErrorString(e)); ok = false; }
+        }
+#else
+        if (ok) gain_sim_run(T, W, dSD, dIO, dGD, 1, P.stage_blocks, P.waves);
+#endif
+        ok = ok && rt::d2h(bins, dB, nwin * 4, nullptr) && rt::d2h(energies, dE, nwin * 8, nullptr) && rt::sync(nullptr);
+    } else if (g) set_err("hipMalloc failed");
+    rt::dfree(src); rt::dfree(dB); rt::dfree(dE); rt::dfree(dIO); rt::dfree(dSD); rt::dfree(dGD); rt::dfree(rows);
+    return ok ? (int)nwin : LHIP_ERR_INTERNAL;
 }
 int lhip_debug_info_toc(const int64_t* frames, size_t ncalls, int kbps, uint8_t* toc) {
     if ((!frames && ncalls) || !toc || kbps <= 0) { set_err("lhip_debug_info_toc: bad argument"); return LHIP_ERR_INTERNAL; }

@@ -137,6 +137,8 @@ struct BatchPlan {
     int crc_mode = 0, crc_parts = 0;
     uint32_t* crc_dst = nullptr;
     std::vector<uint32_t> crc;                     // per stream
+    // { replayGain } streams (lhip_gain.h): the two launches' plan and its descriptors on the device; gain.d is empty for a batch without the option
+    GainPlan gain; const GainDesc* dGD = nullptr;
 };
 
 static bool plan_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, BatchPlan& P) {
@@ -245,6 +247,19 @@ static bool stage_crc(Context* ctx, const std::vector<Job>& jobs, BatchPlan& P, 
     if (!ws.crc_desc.ensure((size_t)S * sizeof(CrcDesc)) || !ws.crc_part.ensure((size_t)parts * 4 + 64) || !ws.crc_out.ensure((size_t)S * 4 + 64)) return false;
     if (!rt::h2d(ws.crc_desc.p, cd.data(), (size_t)S * sizeof(CrcDesc), ctx->stream)) return false;
     P.crc_dst = crc_log ? crc_log : (uint32_t*)ws.crc_out.p;
+    return true;
+}
+// { replayGain } streams: every stream of the batch analyses the n_out samples this call appends to its buffer (Lame.js:1609-1613) -- rows and descriptors
+static bool stage_gain(Context* ctx, const std::vector<Job>& jobs, BatchPlan& P) {
+    WorkSet& ws = ctx->ws; const int S = P.S;
+    std::vector<GainRec*> recs((size_t)S); std::vector<int64_t> n((size_t)S);
+    for (int i = 0; i < S; i++) { recs[i] = jobs[i].s->gain.get(); n[i] = jobs[i].n_out; }
+    if (!gain_plan(recs.data(), n.data(), S, P.gain)) return false;
+    if (P.gain.stage_blocks == 0) return true;
+    if (!ws.gain_rows.ensure(P.gain.row_floats * 4 + 64) || !ws.gain_desc.ensure((size_t)S * sizeof(GainDesc))) return false;
+    gain_bind_rows(P.gain, (float*)ws.gain_rows.p);
+    if (!rt::h2d(ws.gain_desc.p, P.gain.d.data(), (size_t)S * sizeof(GainDesc), ctx->stream)) return false;
+    P.dGD = (const GainDesc*)ws.gain_desc.p;
     return true;
 }
 static bool stage_inputs(Context* ctx, std::vector<Job>& jobs, BatchPlan& P) {
@@ -451,10 +466,12 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     CALL_STAMP(0);                                  // plan + workspace
     if (!stage_inputs(ctx, jobs, P)) return false;
     if (P.crc_mode == 2 && !stage_crc(ctx, jobs, P, crc_log)) return false;
+    if (P.ts->gain_on && !stage_gain(ctx, jobs, P)) return false;
     CALL_STAMP(1);                                  // input copies, descriptors, counters zeroed: enqueued
 
     g_rejected = 0; g_rej_pending = nullptr;
     if (!run_pipeline(ctx, P)) return false;
+    if (P.gain.stage_blocks > 0) { for (int i = 0; i < P.S; i++) if (P.gain.d[i].n > 0) { GainRec& g = *jobs[i].s->gain; g.samples += P.gain.d[i].n; g.cur ^= 1; } }      // (enqueued: the records move on)
     CALL_STAMP(2);                                  // kernels enqueued
     // repair statistics live on the device; they travel with the final synchronisation when there is one, else they are fetched
     // when somebody asks (lhip_last_batch_stats)

@@ -42,6 +42,7 @@ struct WorkSet {
         ath_adjust, ath_limit, E, sb, xr, side, l3, seed, seed_flag, nflagged, slow_list, frame_bytes, desc, in16, rejected, out8, prof, fht, hpf, tot_ener, reval, att_clean, nb1, nb2, fr, out_bytes, vdig, small;
     DevBuf crc_desc, crc_part, crc_out;     // { infoTag } streams only (g_out_crc): per-stream descriptors, span remainders, results
     DevBuf ingest, ingest_desc;             // WAV sample types only (g_ingest): the Float32 planes of the call's new samples, per-stream descriptors
+    DevBuf gain_rows, gain_desc;            // { replayGain } streams only (g_gain_stage, g_gain): history ++ new samples per stream and channel, per-stream descriptors
     PinBuf pin_in, pin_out;     // small host-buffer calls (run_batch): everything that travels in / out, staged once in pinned memory
     // last batch (for debug taps)
     Workspace lastW; int lastC = 0, lastCp = 0; bool have_last = false;
@@ -104,5 +105,6 @@ struct lhip_stream {
     int64_t rs_inbuf_len = 0;      // ... and the length of the persistent input buffer allocated for it (Lame.js:1373-1379)
     bool rs_flushed = false;       // flush() has run: the reference's resampler holds NaN from then on, the stream ends there
     std::unique_ptr<TagTotals> tag;   // { infoTag } streams: what the tag frame will report (lhip_infotag.h); null otherwise
+    std::unique_ptr<GainRec> gain;    // { replayGain } streams: the analysis' device record and sample count (lhip_gain.h); null otherwise
     ~lhip_stream() { rt::dfree(d_state); magic = 0; }
 };

@@ -95,6 +95,7 @@ static int encode_host_pipelined(Context* ctx, const std::vector<lhip_stream*>& 
         (void)rt::sync(cs); (void)rt::sync(ks);
         for (size_t i = 0; i < NS; i++) {
             (void)rt::d2d(strs[i]->d_state, (const uint8_t*)ctx->state_bak.p + i * sizeof(StreamState), sizeof(StreamState), ks);
+            if (strs[i]->gain) strs[i]->gain->moved = true;      // (the units already analysed are in its histogram: lhip_replay_gain refuses from here on)
             strs[i]->mf_size = snap[i].mf; strs[i]->mf_samples_to_encode = snap[i].ste; strs[i]->slot_lag = snap[i].lag; strs[i]->frame_num = snap[i].fn; strs[i]->rs_n_in = snap[i].rs;
         }
         (void)rt::sync(ks);

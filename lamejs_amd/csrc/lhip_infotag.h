@@ -6,7 +6,8 @@
 // Layout: the public Xing / LAME tag format as LAME 3.98 writes it for CBR (VBRTag.js:830-960, 576-804) -- a frame of the stream's own header
 // (padding 0, mode_ext 0) whose body starts where the side information would end (two bytes earlier in a protected stream, where the format
 // places it): "Info", flags 0xF, frames, bytes (audio + this frame), 100 seek points, quality, "LAME3.98r", method, lowpass, peak and the two
-// ReplayGain fields (zero: the reference has no decoder and its gain analysis does not run), flags, bitrate, delay and padding (12 bits each),
+// ReplayGain fields (peak and audiophile zero: the reference has no decoder, and LAME writes no album gain; the radio field is zero too unless the stream was
+// built with { replayGain }: then it is the reference's encoding of the track gain the device analysed, lhip_gain.h), flags, bitrate, delay and padding (12 bits each),
 // misc, one zero byte, preset, music length, music CRC, and the CRC-16 of every byte in front of that last field (190 of them in an
 // unprotected MPEG-1 two-channel frame, the number the format's description names).
 #pragma once
@@ -113,7 +114,7 @@ static void tag_placeholder(const Tables& T, const InfoTagCfg& G, uint8_t* f) {
     tag_header(T, f);
     if (T.error_protection) { const uint32_t c = tag_iso_crc(f, T.sideinfo_len); f[4] = (uint8_t)(c >> 8); f[5] = (uint8_t)c; }
 }
-static void tag_write(const Tables& T, const InfoTagCfg& G, const TagTotals& v, uint8_t* f) {
+static void tag_write(const Tables& T, const InfoTagCfg& G, const TagTotals& v, uint8_t* f, uint32_t radio_gain = 0) {
     memset(f, 0, (size_t)G.size);
     tag_header(T, f);
     int p = T.sideinfo_len - (T.error_protection ? 2 : 0);
@@ -126,7 +127,7 @@ static void tag_write(const Tables& T, const InfoTagCfg& G, const TagTotals& v, 
     be32((uint32_t)G.quality);
     memcpy(f + p, G.version, 9); p += 9;
     f[p++] = (uint8_t)G.method; f[p++] = (uint8_t)G.lowpass;
-    be32(0); be16(0); be16(0);                                   // peak signal amplitude, radio and audiophile ReplayGain
+    be32(0); be16(radio_gain); be16(0);                          // peak signal amplitude (no decoder: zero), radio ReplayGain ({ replayGain } streams, else zero), audiophile (LAME writes none)
     f[p++] = (uint8_t)G.flags;
     f[p++] = (uint8_t)(T.brate >= 255 ? 255 : T.brate);
     const uint32_t delay = (uint32_t)G.delay & 0xfff, pad = (uint32_t)(v.padding < 0 ? 0 : (int64_t)v.padding) & 0xfff;      // (a fraction is cut as `>>` cuts it)

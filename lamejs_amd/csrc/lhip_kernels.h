@@ -275,6 +275,17 @@ __global__ __launch_bounds__(64) void g_ingest(const IngestDesc* D, int nstreams
     const unsigned bad = kb_ingest(D, s, (int64_t)blockIdx.x - D[s].blk0, threadIdx.x, L, limit);
     if (ctr && bad && threadIdx.x == 0) atomicAdd(ctr, (unsigned long long)bad);
 }
+// ReplayGain of { replayGain } streams (k_gain.h): a lane per position of a stream's row (history ++ new samples), then a wave per 64 completed windows of a stream.
+// Launched only for a batch of such streams, once the call's samples exist.
+__global__ __launch_bounds__(GAIN_STAGE_NT) void g_gain_stage(Tables T, Workspace W, const StreamDesc* SD, const StreamIO* IO, const GainDesc* D, int nstreams) {
+    const int s = gain_find_stream<true>(D, nstreams, (int)blockIdx.x);
+    kb_gain_stage(T, W, SD, IO, D, s, (int64_t)((int)blockIdx.x - D[s].blk0) * GAIN_STAGE_NT + threadIdx.x);
+}
+template <int CH> __global__ __launch_bounds__(64) void g_gain(const GainDesc* D, int nstreams) {
+    __shared__ float L[64 * CH * GAIN_STRIDE];
+    const int s = gain_find_stream<false>(D, nstreams, (int)blockIdx.x);
+    kb_gain<CH>(D, s, (int)blockIdx.x - D[s].wave0, threadIdx.x, L);
+}
 __global__ __launch_bounds__(64) void g_out_crc_fold(const CrcDesc* D, const uint32_t* partial, uint32_t* out) { kb_crc_fold(D, blockIdx.x, threadIdx.x, partial, out); }
 #ifndef LHIP_FRAME_PIPE
 #define LHIP_FRAME_PIPE 1      /* 0: the Huffman counts of the outer loop on the searching wave itself (A/B builds) */
@@ -357,8 +368,8 @@ template <int RESV> __global__ __launch_bounds__(64 * FR_WAVES) void g_frame(QAr
 #endif
 }
 // optional per-kernel timing with HIP events on the launch stream (bench.py roofline accounting)
-enum { KT_LOAD, KT_PREP, KT_PSYA, KT_SCAN, KT_PSYB, KT_POLY, KT_MDCT, KT_QUANT, KT_VALIDATE, KT_REPAIR, KT_BITS, KT_SAVE, KT_COUNT, KT_OUT_CRC, KT_INGEST, KT_N };
-static const char* const g_kt_names[KT_N] = {"load", "prep", "psyA", "scan", "psyB", "polyphase", "mdct", "quant", "validate", "repair", "bits", "save", "count_rejected", "out_crc", "ingest"};
+enum { KT_LOAD, KT_PREP, KT_PSYA, KT_SCAN, KT_PSYB, KT_POLY, KT_MDCT, KT_QUANT, KT_VALIDATE, KT_REPAIR, KT_BITS, KT_SAVE, KT_COUNT, KT_OUT_CRC, KT_INGEST, KT_GAIN_STAGE, KT_GAIN, KT_N };
+static const char* const g_kt_names[KT_N] = {"load", "prep", "psyA", "scan", "psyB", "polyphase", "mdct", "quant", "validate", "repair", "bits", "save", "count_rejected", "out_crc", "ingest", "gain_stage", "gain"};
 // The switch is process-wide (bench.py turns it on for one extra, untimed step); the events of a batch belong to the calling
 // thread (a batch runs entirely inside one run_batch call), the accumulators are shared by all devices and guarded by g_kt_mu.
 static std::atomic<bool> g_kt_on{false};

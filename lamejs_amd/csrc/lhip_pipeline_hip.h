@@ -149,5 +149,11 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
         LAUNCH(KT_OUT_CRC, g_out_crc, P.crc_parts, st, (const CrcDesc*)ws.crc_desc.p, S, (uint32_t*)ws.crc_part.p);
         LAUNCH(KT_OUT_CRC, g_out_crc_fold, S, st, (const CrcDesc*)ws.crc_desc.p, (const uint32_t*)ws.crc_part.p, P.crc_dst);
     }
+    // { replayGain } streams: the samples of the call exist by now (caller's samples / g_ingest's planes / the resampler's plane) -- rows, then one lane per completed window
+    if (P.gain.stage_blocks > 0) {
+        P.paths |= LHIP_PATH_GAIN;
+        LAUNCHB(KT_GAIN_STAGE, g_gain_stage, P.gain.stage_blocks, GAIN_STAGE_NT, st, T, W, dSD, dIO, P.dGD, S);
+        if (C == 2) LAUNCH(KT_GAIN, g_gain<2>, P.gain.waves, st, P.dGD, S); else LAUNCH(KT_GAIN, g_gain<1>, P.gain.waves, st, P.dGD, S);
+    }
     return true;
 }

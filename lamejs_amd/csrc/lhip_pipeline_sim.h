@@ -16,6 +16,15 @@
 #else
 #define QUANT_RUN(chain_) WAVE_RUN(kb_quant<0, 0>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ, QT))
 #endif
+// g_gain_stage and g_gain over a launch's descriptors (also lhip_debug_gain_windows)
+static void gain_sim_run(const Tables& T, const Workspace& W, const StreamDesc* SD, const StreamIO* IO, const GainDesc* D, int S, int stage_blocks, int waves) {
+    static thread_local float LG[LHIP_NL * 2 * GAIN_STRIDE];
+    for (int b = 0; b < stage_blocks; b++) { const int s = gain_find_stream<true>(D, S, b); for (int t = 0; t < GAIN_STAGE_NT; t++) kb_gain_stage(T, W, SD, IO, D, s, (int64_t)(b - D[s].blk0) * GAIN_STAGE_NT + t); }
+    for (int b = 0; b < waves; b++) {
+        const int s = gain_find_stream<false>(D, S, b);
+        if (D[s].channels == 2) WAVE_RUN(kb_gain<2>(D, s, b - D[s].wave0, lane_, LG)); else WAVE_RUN(kb_gain<1>(D, s, b - D[s].wave0, lane_, LG));
+    }
+}
 static inline bool g_kt_on_() { return false; }
 static bool collect_kernel_times(void*) { return true; }
 static bool collect_repair_stats(Context*, BatchPlan&, bool, const int32_t*) { return true; }      // (run_pipeline counted them itself)
@@ -171,6 +180,10 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
         const CrcDesc* D = (const CrcDesc*)ctx->ws.crc_desc.p; uint32_t* part = (uint32_t*)ctx->ws.crc_part.p;
         for (int b = 0; b < P.crc_parts; b++) { const int s = crc_find_stream(D, S, b); WAVE_RUN(kb_out_crc(D, s, b - D[s].part0, lane_, part)); }
         for (int s = 0; s < S; s++) WAVE_RUN(kb_crc_fold(D, s, lane_, part, P.crc_dst));
+    }
+    if (P.gain.stage_blocks > 0) {      // g_gain_stage and g_gain, workgroup by workgroup
+        P.paths |= LHIP_PATH_GAIN;
+        gain_sim_run(T, W, dSD, dIO, P.dGD, S, P.gain.stage_blocks, P.gain.waves);
     }
     return true;
 }

@@ -15,8 +15,9 @@ struct TableSet {
     void* d_qtabs = nullptr;
     int device = 0;
     int base_frame_bytes = 0;
-    bool bad_option = false;  // build_tables refused an option of the blob -- input gains, frame protection, header flags, the Info tag (lhip_create: -3)
+    bool bad_option = false;  // build_tables refused an option of the blob -- input gains, frame protection, header flags, the Info tag, ReplayGain (lhip_create: -3)
     InfoTagCfg tag;           // { infoTag } (lhip_infotag.h): host-side only, no kernel sees it
+    int gain_on = 0;          // { replayGain } (lhip_gain.h): the streams of this blob analyse the samples they consume; host-side only
     ~TableSet() { rt::dfree(d_blob); rt::dfree(d_extra); rt::dfree(d_qtabs); }
 };
 
@@ -100,6 +101,7 @@ static bool parse_blob(TableSet& ts, const void* blob, size_t nbytes, void* stre
         if (G.on && (!tv || tv->dtype != 1 || tv->count != 9)) { set_err("tables blob: entry missing: tag_version"); ok = false; }
         else if (G.on) for (int i = 0; i < 9; i++) G.version[i] = (uint8_t)((const int32_t*)(b + tv->offset))[i];
     }
+    { const int k_ = named("cfg_i_names", "replay_gain"); ts.gain_on = k_ >= 0 ? ci[k_] : 0; }      // { replayGain }: only a blob built with the option has the entry
 #undef CIO
 #undef CDO
     optional = false;
@@ -193,6 +195,13 @@ static bool check_envelope(TableSet& ts, const lhip_config& cfg) {
                     std::to_string((int)TAG_BODY_BYTES) + ", at most " + std::to_string((int)TAG_MAX_FRAME) + ")");
             ts.bad_option = true; return false;
         }
+    }
+    // ReplayGain (extension { replayGain }): the analysis reads the samples behind the resampler where the kernels leave them -- a non-integer-ratio stream's flush is
+    // partly host stand-ins that no kernel sees, so there is no complete sample stream to analyse
+    if (ts.gain_on) {
+        if (ts.gain_on != 1) { set_err("ReplayGain: replay_gain is 0 or 1"); ts.bad_option = true; return false; }
+        if (T.rs_frac) { set_err("ReplayGain cannot be combined with fractionalResample (the flush's frames are partly host stand-ins: the analysed sample stream would be incomplete)"); ts.bad_option = true; return false; }
+        if (gain_rate_index(T.out_samplerate) < 0) { set_err("ReplayGain: no filter for an output sample rate of " + std::to_string(T.out_samplerate)); ts.bad_option = true; return false; }
     }
     return true;
 }

@@ -45,6 +45,7 @@ static int (*p_seek)(lhip_stream*, int64_t, const int16_t*, const int16_t*);
 static int64_t (*p_call_limit)(const lhip_stream*);
 static int (*p_stream_info)(const lhip_stream*, lhip_stream_info_t*);
 static int64_t (*p_info_tag)(lhip_stream*, uint8_t*, size_t);
+static int (*p_replay_gain)(lhip_stream*, int32_t*, int64_t*, int64_t*);
 
 static int load_lib(napi_env env) {
     if (g_lib) return 1;
@@ -67,7 +68,7 @@ static int load_lib(napi_env env) {
     SYM(p_state_bytes, "lhip_state_bytes") SYM(p_state_get, "lhip_state_get") SYM(p_state_set, "lhip_state_set")
     SYM(p_seek_tail, "lhip_seek_tail_samples") SYM(p_seek, "lhip_seek") SYM(p_out_bytes, "lhip_encode_output_bytes")
     SYM(p_call_limit, "lhip_frac_call_limit") SYM(p_encode_pcm, "lhip_encode_pcm") SYM(p_encode_batch_pcm, "lhip_encode_batch_pcm")
-    SYM(p_stream_info, "lhip_stream_info") SYM(p_info_tag, "lhip_info_tag")
+    SYM(p_stream_info, "lhip_stream_info") SYM(p_info_tag, "lhip_info_tag") SYM(p_replay_gain, "lhip_replay_gain")
 #undef SYM
     return 1;
 }
@@ -352,6 +353,23 @@ static napi_value js_info_tag(napi_env env, napi_callback_info info) {
     if (n < 0) { napi_throw_error(env, NULL, p_last_error()); return NULL; }
     return make_i8(env, out, (size_t)n);
 }
+/* { replayGain } streams (include/lamejs_hip.h, "ReplayGain"): { tenthDb (null while no window is complete), windows, samples }; throws for a stream built
+ * without the option or one that was moved.  Waits for the stream's device. */
+static napi_value js_replay_gain(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1], r, v;
+    napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
+    lhip_stream* s = argc >= 1 ? handle_arg(env, argv[0]) : NULL;
+    if (!s) return NULL;
+    int32_t tenth = 0; int64_t windows = 0, samples = 0;
+    const int rc = p_replay_gain(s, &tenth, &windows, &samples);
+    if (rc < 0) { napi_throw_error(env, NULL, p_last_error()); return NULL; }
+    napi_create_object(env, &r);
+    if (rc == 0) napi_create_int32(env, tenth, &v); else napi_get_null(env, &v);
+    napi_set_named_property(env, r, "tenthDb", v);
+    napi_create_int64(env, windows, &v); napi_set_named_property(env, r, "windows", v);
+    napi_create_int64(env, samples, &v); napi_set_named_property(env, r, "samples", v);
+    return r;
+}
 static napi_value js_seek_tail(napi_env env, napi_callback_info info) {
     size_t argc = 1; napi_value argv[1], r;
     napi_get_cb_info(env, info, &argc, argv, NULL, NULL);
@@ -410,7 +428,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"setDevices", 0, js_set_devices, 0, 0, 0, napi_default, 0},
         {"seekTailSamples", 0, js_seek_tail, 0, 0, 0, napi_default, 0}, {"callLimit", 0, js_call_limit, 0, 0, 0, napi_default, 0}, {"seek", 0, js_seek, 0, 0, 0, napi_default, 0},
         {"stateGet", 0, js_state_get, 0, 0, 0, napi_default, 0}, {"stateSet", 0, js_state_set, 0, 0, 0, napi_default, 0},
-        {"streamInfo", 0, js_stream_info, 0, 0, 0, napi_default, 0}, {"infoTag", 0, js_info_tag, 0, 0, 0, napi_default, 0}};
+        {"streamInfo", 0, js_stream_info, 0, 0, 0, napi_default, 0}, {"infoTag", 0, js_info_tag, 0, 0, 0, napi_default, 0},
+        {"replayGain", 0, js_replay_gain, 0, 0, 0, napi_default, 0}};
     napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
     return exports;
 }

@@ -37,6 +37,12 @@
  * counts, a 100-point seek table, encoder delay and end padding for gapless playback, the CRC-16 of the audio, LAME's extension fields -- as an Int8Array
  * to be written over the placeholder at offset 0.  With every option above, encodeBatch() of tagged beside untagged encoders and { pendingFrames }
  * included; refused at construction where a frame is too small to hold the tag (8 kHz at 8 kbps, say) and on a { fractionalResample } stream that resamples.
+ * Extension { replayGain: true }: the samples the encoder consumes (behind gains, downmix and resampler; the zeros of flush() included; left and right of a
+ * joint-stereo stream) are analysed on the GPU as the reference core's ReplayGain analysis does -- the published filters, windows of a twentieth of a second,
+ * the 95th percentile of their levels -- and enc.replayGain() returns { tenthDb, windows, samples }: the track gain in tenths of a dB.  The result does not
+ * depend on how the stream is cut into calls; nothing is read back until replayGain() or infoTagFrame() asks.  With { infoTag } the tag frame's radio
+ * ReplayGain field carries the value (peak amplitude and the audiophile field stay zero).  With every option above, encodeBatch() of such encoders beside
+ * others and { pendingFrames } included; refused at construction on a { fractionalResample } stream that resamples; not after seek() / setState().
  * Extension { fractionalResample: true }: the 49 (channels, sample rate, kbps) triples the reference resamples by a non-integer ratio -- refused
  * by default, because the reference feeds itself NaN samples there once a call is long enough -- are accepted as call-sequence streams: every
  * encodeBuffer() gives the reference's bytes for the same sequence of call lengths; a call longer than the reference consumes whole throws
@@ -69,7 +75,7 @@ const blobCache = new Map();
 function tablesBlob(channels, samplerate, kbps, opts) {
     const key = [channels, samplerate, kbps, opts && opts.jointStereo ? 1 : 0, opts && opts.reservoir ? 1 : 0, opts && opts.fractionalResample ? 1 : 0,
         opts && opts.downmix ? 1 : 0, opts ? String(opts.scale) : '', opts ? String(opts.scaleLeft) : '', opts ? String(opts.scaleRight) : '',
-        opts ? ['protect', 'copyright', 'original', 'privateBit', 'emphasis'].map((k) => String(opts[k])).join(',') : '', opts && opts.infoTag ? 1 : 0].join('|');     /* (pendingFrames is host-side only) */
+        opts ? ['protect', 'copyright', 'original', 'privateBit', 'emphasis'].map((k) => String(opts[k])).join(',') : '', opts && opts.infoTag ? 1 : 0, opts && opts.replayGain ? 1 : 0].join('|');     /* (pendingFrames is host-side only) */
     let blob = blobCache.get(key);
     if (!blob) { blob = tables.buildBlob(channels, samplerate, kbps, opts).blob; blobCache.set(key, blob); }
     return blob;
@@ -222,6 +228,9 @@ function Mp3Encoder(channels, samplerate, kbps, opts) {
     /* { infoTag }: the stream's totals so far; after flush() the finished Info/LAME tag frame, to be written over the placeholder at offset 0 */
     this.streamInfo = function () { return native.streamInfo(handle); };
     this.infoTagFrame = function () { noPending('infoTagFrame'); return native.infoTag(handle); };
+    /* { replayGain }: { tenthDb, windows, samples } -- the track gain in tenths of a dB (null while no window of ceil(rate / 20) samples is complete), the
+     * complete windows and the samples analysed so far (samples still held back by { pendingFrames } are not among them) */
+    this.replayGain = function () { return native.replayGain(handle); };
 }
 
 /* RIFF/WAVE header reader with the reference's field names (index.js:138-193) */

@@ -245,6 +245,10 @@ function resolveParams(channels, samplerate, kbps, opts) {
          * non-integer-ratio stream is partly host stand-ins and its padding fractional: lhip_create refuses the tag there (-3), as it refuses a
          * configuration whose frames are too small to hold it */
         p.info_tag = flag('infoTag', 0);
+        /* extension { replayGain }: the stream analyses the samples its encoder consumes (the reference core's gfc.findReplayGain, Lame.js:1609-1613) on the
+         * device; lhip_replay_gain reports the track gain and, with { infoTag }, the tag's radio field carries it.  lhip_create refuses it (-3) where the stream
+         * resamples by a non-integer ratio */
+        p.replay_gain = flag('replayGain', 0);
     }
 
     /* CBR: ABR preset row for this bitrate (Lame.js:1202-1230, Presets.js:270-357) */
@@ -699,6 +703,8 @@ function buildBlob(channels, samplerate, kbps, opts) {
         tagVersion = 'LAME' + C.lame_short_version.split('.').slice(0, 2).join('.') + 'r';          /* Version.js:56-59 getLameVeryShortVersion */
         if (tagVersion.length != 9) throw new Error('lamejs_amd: the very short version string must have 9 characters');
     }
+    /* { replayGain }: one named entry that exists only with the option (a blob without it is the bytes it always was) */
+    if (p.replay_gain) Object.assign(cfg_i, { replay_gain: 1 });
     const entries = [];
     entries.push(['cfg_i_names', Int32Array.from(Buffer.from(Object.keys(cfg_i).join(',') + '\0', 'ascii'))]);
     entries.push(['cfg_i', I(Object.values(cfg_i))]);
@@ -759,12 +765,12 @@ module.exports = { buildBlob, resolveParams, buildTables, packBlob, sourceHash, 
 
 if (require.main === module) {
     /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] [fracresample] [downmix] [scale=G] [scaleLeft=G] [scaleRight=G]
-     *      [protect] [copyright] [original=0|1] [privateBit] [emphasis=E] [infoTag] */
+     *      [protect] [copyright] [original=0|1] [privateBit] [emphasis=E] [infoTag] [replayGain] */
     const [ch, sr, kb, out] = process.argv.slice(2), flags = process.argv.slice(6);
     const opts = { jointStereo: flags.includes('joint'), reservoir: flags.includes('reservoir'), fractionalResample: flags.includes('fracresample') };
     if (flags.includes('downmix')) opts.downmix = true;
     for (const f of flags) { const m = /^(scale|scaleLeft|scaleRight)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
-    for (const k of ['protect', 'copyright', 'privateBit', 'infoTag']) if (flags.includes(k)) opts[k] = true;
+    for (const k of ['protect', 'copyright', 'privateBit', 'infoTag', 'replayGain']) if (flags.includes(k)) opts[k] = true;
     for (const f of flags) { const m = /^(original|emphasis)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
     const r = buildBlob(+ch, +sr, +kb, opts);
     require('fs').writeFileSync(out, r.blob);
