@@ -329,7 +329,8 @@ int lhip_debug_ingest(int format, int channels, const void* bytes, size_t nsampl
 
 /* Debug/test taps (tests only): copy intermediate results of the most recent batch to the host.
  * what: 0 xr [granule][ch][576] f32, 1 blocktype [granule][ch] i32, 2 E [granule][psy ch][122] f32 (psy ch = ch, or L R mid side in joint stereo; thresholds
- * handed to the quantizer for that granule), 3 ath_adjust [frame] f64, 4 side records (struct GrSide).
+ * handed to the quantizer for that granule), 3 ath_adjust [frame] f64, 4 side records (struct GrSide); simulation libraries only: 10 two i64, the
+ * evaluations of the quantization search this process has made without / with the last round of pairs (lines 512..575 all zero / not).
  * Returns bytes copied or <0. */
 int64_t lhip_debug_read(int what, void* dst, size_t cap);
 

@@ -27,6 +27,7 @@ struct GI {   // wave-uniform scalar part of the reference's GrInfo
     int part2_length, sfb_lmax, sfb_smin, psy_lmax, sfbmax, psymax, sfbdivide;
     int count1bits, max_nonzero_coeff;
     int firstcut;               // first band reaching past max_nonzero_coeff (64: none): fixed once max_nonzero_coeff is (q_set_firstcut)
+    int tail0;                  // every line of 512..575 is +-0 (q_calc_xmin): the pairs 256..287 quantize to zero and their round is not issued (NPL_HEAD)
 };
 
 struct NoiseRes { double max_noise; int over_count, over_SSD, bits; };
@@ -43,7 +44,7 @@ LHIP_DEV void uni_gi(GI& g) {
     g.region0_count = uni(g.region0_count); g.region1_count = uni(g.region1_count); g.preflag = uni(g.preflag); g.scalefac_scale = uni(g.scalefac_scale);
     g.count1table_select = uni(g.count1table_select); g.part2_length = uni(g.part2_length); g.sfb_lmax = uni(g.sfb_lmax); g.sfb_smin = uni(g.sfb_smin);
     g.psy_lmax = uni(g.psy_lmax); g.sfbmax = uni(g.sfbmax); g.psymax = uni(g.psymax); g.sfbdivide = uni(g.sfbdivide);
-    g.count1bits = uni(g.count1bits); g.max_nonzero_coeff = uni(g.max_nonzero_coeff); g.firstcut = uni(g.firstcut);
+    g.count1bits = uni(g.count1bits); g.max_nonzero_coeff = uni(g.max_nonzero_coeff); g.firstcut = uni(g.firstcut); g.tail0 = uni(g.tail0);
 }
 
 // optional phase profiling (build with -DLHIP_PHASE_PROF; never in the product library)
@@ -348,7 +349,7 @@ LHIP_DEV void q_init_outer_loop(const Tables& T, const PowBase& pb10, double ath
     g.part2_length = 0; g.sfb_lmax = SBPSY_l; g.sfb_smin = SBPSY_s;
     g.psy_lmax = T.sfb21_extra ? SBMAX_l : SBPSY_l;
     g.psymax = g.psy_lmax; g.sfbmax = g.sfb_lmax; g.sfbdivide = 11;
-    g.count1bits = 0; g.max_nonzero_coeff = 575; g.xrpow_max = 0; g.firstcut = 64;
+    g.count1bits = 0; g.max_nonzero_coeff = 575; g.xrpow_max = 0; g.firstcut = 64; g.tail0 = 0;
     int nsfb;
     if (block_type == SHORT_TYPE) {
         g.sfb_smin = 0; g.sfb_lmax = 0;
@@ -486,9 +487,18 @@ LHIP_DEV void fold_band_sums(double (&tq)[NLN_FOLD], const uint8_t* l2s, int max
     wave_sync();
 }
 
-// calc_xmin (QuantizePVT.js:569-719), CBR flavour
+// The granule-channel's own spectrum decides whether the last round of pairs (lines 512..575) is dead: true exactly when all of them
+// compare equal to zero.  Not derived from max_nonzero_coeff -- the reference's 575 for short blocks stays what it is (firstcut and the
+// walk depend on it), and a short block's windows 1 and 2 put lines there that a long block at the same bitrate never has.
+LHIP_DEV int q_tail_is_zero(int lane, const QuantLds& L) {
+    int nz = 0;
+    for (int k = 512 + lane; k < 576; k += LHIP_NL) if (!((double)L.xr[k] == 0)) nz = 1;
+    return !wave_any(nz);
+}
+
+// calc_xmin (QuantizePVT.js:569-719), CBR flavour; want_tail0: also set g.tail0 (the kernels that skip the dead round of pairs)
 LHIP_DEV void q_calc_xmin(const Tables& T, double ath_adjust, double masking_lower, const float* ratio /*E layout*/,
-                          GI& g, int lane, QuantLds& L, const QuantTabs& Q) {
+                          GI& g, int lane, QuantLds& L, const QuantTabs& Q, const int want_tail0 = 0) {
     lane = fresh_lane(lane);
     // band energies en0 = sum of xr^2 in line order: terms with all lanes busy, then the ordered fold
     {
@@ -517,6 +527,7 @@ LHIP_DEV void q_calc_xmin(const Tables& T, double ath_adjust, double masking_low
         for (int k = lane; k < 576; k += LHIP_NL) if (!((double)L.xr[k] == 0)) t = k;
         t = wave_max(t);
         g.max_nonzero_coeff = (t >= 575) ? 575 : t + 1;
+        if (want_tail0) g.tail0 = t < 512;
     } else {
         LHIP_LANE_ONCE(sfb, 0, SBPSY_s) {       // psymax/3 bands, 3 windows each
             const double tmpATH = ath_adjust * (double)T.ATH_s[sfb];
@@ -540,6 +551,7 @@ LHIP_DEV void q_calc_xmin(const Tables& T, double ath_adjust, double masking_low
             L.rxmin[3 * sfb] = recip_for_div((double)px[0]); L.rxmin[3 * sfb + 1] = recip_for_div((double)px[1]); L.rxmin[3 * sfb + 2] = recip_for_div((double)px[2]);
         }
         g.max_nonzero_coeff = 575;
+        if (want_tail0) g.tail0 = q_tail_is_zero(lane, L);
     }
     q_set_firstcut(g, lane, L);
     wave_sync();
@@ -552,8 +564,22 @@ LHIP_DEV void q_calc_xmin(const Tables& T, double ath_adjust, double masking_low
 // xrpow comes in as one 8-byte load and ix goes out as one 32-bit store per pair, and the quantized values stay in
 // registers (vx, vy) for the Huffman bit count that follows -- no LDS round trip between the two.
 enum { NPL = (288 + LHIP_NL - 1) / LHIP_NL };
+// The pairs 256..287 (lines 512..575) are the last round, on half the lanes.  Up to 256 kbps the encoder's lowpass leaves those lines
+// exactly zero in a long block, so they quantize to zero whatever the gain: with GI::tail0 set the per-pair functions run NR = NPL_HEAD
+// rounds, and the words 256..287 of the working spectrum are zeroed once per granule-channel instead (q_unit).
+enum { NPL_HEAD = 256 / LHIP_NL };
+#if defined(LHIP_HOSTSIM)
+// how many evaluations (quantize + count) ran with the short and with the full round count: lhip_debug_read(10), for the tests that must
+// see both forms at work
+struct RoundStats { long head = 0, full = 0; };      // (atomic adds: the simulations may run on several host threads)
+inline RoundStats& round_stats() { static RoundStats t; return t; }
+#define LHIP_ROUND_COUNT(f) do { if (lane == 0) __atomic_fetch_add(&round_stats().f, 1L, __ATOMIC_RELAXED); } while (0)
+#else
+#define LHIP_ROUND_COUNT(f) do { } while (0)
+#endif
+template <int NR>
 LHIP_DEV void q_quantize(const Tables& T, const GI& g, const int32_t* scalefac, int16_t* ix, int use_prev,
-                         int pn_gain, int pn_sfb_count1, int (&vx)[NPL], int (&vy)[NPL], int lane, QuantLds& L, const QuantTabs& Q) {
+                         int pn_gain, int pn_sfb_count1, int (&vx)[NR], int (&vy)[NR], int lane, QuantLds& L, const QuantTabs& Q) {
     lane = fresh_lane(lane);
     const double istep = ipow20(Q, g.global_gain);
     // every truncated product is <= xrpow_max * istep: below QT_N no lane can need the part of adj43 that is not staged in LDS
@@ -564,9 +590,9 @@ LHIP_DEV void q_quantize(const Tables& T, const GI& g, const int32_t* scalefac, 
     // non-cached band reaching past max_nonzero_coeff (sstar) is quantized partially and ends the walk
     unsigned long long tm_ = PH_NOW(); (void)tm_;
     // the lines first: their LDS latency passes while the band masks are formed
-    float xa[NPL], xb[NPL];
+    float xa[NR], xb[NR];
 #pragma unroll
-    for (int j = 0; j < NPL; j++) {
+    for (int j = 0; j < NR; j++) {
         const int p = 2 * (lane + LHIP_NL * j);
         xa[j] = 0.f; xb[j] = 0.f;
         if (p < 576) { struct F2 { float x, y; }; const F2 xx = *(const F2*)(L.xrpow + p); xa[j] = xx.x; xb[j] = xx.y; }   // 8-byte aligned: p is even
@@ -597,17 +623,17 @@ LHIP_DEV void q_quantize(const Tables& T, const GI& g, const int32_t* scalefac, 
     const float istep_f = Q.ipow20[g.global_gain];     // the Float32Array value itself; `istep` above is its f64 image
     // staged, branch-light form: all loads of a stage are independent so they overlap (LDS latency is the cost here); the two
     // truncations of every line are q_floor_prod / q_floor_fma (lhip_math.h)
-    int ra[NPL], rb[NPL];
+    int ra[NR], rb[NR];
     q_floor_prod(xa, xb, istep_f, ra, rb);                                 // 0 <= x <= 8206: truncation == ToInt32
-    float aa[NPL], ab[NPL];
+    float aa[NR], ab[NR];
     if (!may_big) {                                                        // every product is below QT_N (see may_big): nothing to clamp
 #pragma unroll
-        for (int j = 0; j < NPL; j++) { aa[j] = Q.adj43[ra[j]]; ab[j] = Q.adj43[rb[j]]; }
+        for (int j = 0; j < NR; j++) { aa[j] = Q.adj43[ra[j]]; ab[j] = Q.adj43[rb[j]]; }
     } else {                                                               // rare: large quantized values
 #pragma unroll
-        for (int j = 0; j < NPL; j++) { aa[j] = Q.adj43[ra[j] < QT_N ? ra[j] : QT_N - 1]; ab[j] = Q.adj43[rb[j] < QT_N ? rb[j] : QT_N - 1]; }
+        for (int j = 0; j < NR; j++) { aa[j] = Q.adj43[ra[j] < QT_N ? ra[j] : QT_N - 1]; ab[j] = Q.adj43[rb[j] < QT_N ? rb[j] : QT_N - 1]; }
 #pragma unroll
-        for (int j = 0; j < NPL; j++) {
+        for (int j = 0; j < NR; j++) {
             if (ra[j] >= QT_N) aa[j] = T.adj43[ra[j]];
             if (rb[j] >= QT_N) ab[j] = T.adj43[rb[j]];
         }
@@ -617,14 +643,14 @@ LHIP_DEV void q_quantize(const Tables& T, const GI& g, const int32_t* scalefac, 
     if (!need_old && m_zo == 0) {
         // the common round (every bin-search round and most others): no cached band, no 0/1 shortcut
 #pragma unroll
-        for (int j = 0; j < NPL; j++) {
+        for (int j = 0; j < NR; j++) {
             const int p = 2 * (lane + LHIP_NL * j);
             if (p < 576) *(uint32_t*)(ix + p) = (uint32_t)vx[j] | ((uint32_t)vy[j] << 16);
         }
     } else if (m_zo == 0) {
         // cached bands keep their values, nothing else
 #pragma unroll
-        for (int j = 0; j < NPL; j++) {
+        for (int j = 0; j < NR; j++) {
             const int p = 2 * (lane + LHIP_NL * j);
             int sf = 0; uint32_t oldw = 0;
             if (p < 576) { sf = l2s[p]; oldw = *(const uint32_t*)(ix + p); }
@@ -642,7 +668,7 @@ LHIP_DEV void q_quantize(const Tables& T, const GI& g, const int32_t* scalefac, 
         if ((double)zo_thr < compareval0) zo_thr = f32_next_up(zo_thr);
         // the previous values are only fetched when some band is cached
 #pragma unroll
-        for (int j = 0; j < NPL; j++) {
+        for (int j = 0; j < NR; j++) {
             const int p = 2 * (lane + LHIP_NL * j);
             int sf = 0; uint32_t oldw = 0;
             if (p < 576) { sf = l2s[p]; if (need_old) oldw = *(const uint32_t*)(ix + p); }
@@ -785,7 +811,8 @@ LHIP_DEV int apply_cond_fields(int state, int asg) {
 
 // noquant_count_bits (Takehiro.js:521-628); updates g, returns bits.  pn_sfb_count1 as in/out.
 // *asg_mask: which conditionally assigned fields this call wrote (see pack_cond_fields).
-LHIP_DEV int q_noquant_count_bits(const Tables& T, GI& g, const int16_t* ix, int (&vx)[NPL], int (&vy)[NPL], int use_prev, int* pn_sfb_count1, int* asg_mask, int lane, QuantLds& L, const QuantTabs& Q) {
+template <int NR>
+LHIP_DEV int q_noquant_count_bits(const Tables& T, GI& g, const int16_t* ix, int (&vx)[NR], int (&vy)[NR], int use_prev, int* pn_sfb_count1, int* asg_mask, int lane, QuantLds& L, const QuantTabs& Q) {
     *asg_mask = 0;
     lane = fresh_lane(lane);
     unsigned long long tm_ = PH_NOW(); (void)tm_;
@@ -800,7 +827,7 @@ LHIP_DEV int q_noquant_count_bits(const Tables& T, GI& g, const int16_t* ix, int
 #if LHIP_NL == 1
     {
         int top = 0;
-        for (int j = 0; j < NPL; j++) if ((vx[j] | vy[j]) != 0) top = 2 * (lane + LHIP_NL * j) + 2;
+        for (int j = 0; j < NR; j++) if ((vx[j] | vy[j]) != 0) top = 2 * (lane + LHIP_NL * j) + 2;
         i = top;
         const int nq = i >> 2;
         firstbig = nq;
@@ -815,7 +842,7 @@ LHIP_DEV int q_noquant_count_bits(const Tables& T, GI& g, const int16_t* ix, int
         // answered on the scalar unit: no reduction chain, no second pass over the spectrum.
         int tp = -1, bp = -1;                    // highest non-zero pair / highest pair with a value > 1
 #pragma unroll
-        for (int j = 0; j < NPL; j++) {
+        for (int j = 0; j < NR; j++) {
             const uint64_t nz = wave_ballot((vx[j] | vy[j]) != 0), bg = wave_ballot((vx[j] | vy[j]) > 1);
             if (nz) tp = 64 * j + 63 - (int)__builtin_clzll(nz);
             if (bg) bp = 64 * j + 63 - (int)__builtin_clzll(bg);
@@ -866,9 +893,9 @@ LHIP_DEV int q_noquant_count_bits(const Tables& T, GI& g, const int16_t* ix, int
     *asg_mask = (g.block_type != SHORT_TYPE ? 8 : 0) | (use2 ? 4 : 0) | (0 < a1 ? 1 : 0) | (a1 < a2 ? 2 : 0);
     // region maxima: region of a pair = number of boundaries at or below it
     int m0 = 0, m1 = 0, m2 = 0;
-    int rj[NPL];                                                    // region of the lane's pairs (3: at or beyond big_values), kept for the length sums
+    int rj[NR];                                                    // region of the lane's pairs (3: at or beyond big_values), kept for the length sums
 #pragma unroll
-    for (int j = 0; j < NPL; j++) {
+    for (int j = 0; j < NR; j++) {
         rj[j] = 3;
         if (2 * LHIP_NL * j >= i) continue;                         // wave-uniform: every pair of this round of lanes lies beyond big_values
         const int p = 2 * (lane + LHIP_NL * j);
@@ -918,7 +945,7 @@ LHIP_DEV int q_noquant_count_bits(const Tables& T, GI& g, const int16_t* ix, int
     const int any_esc = (m0 > 15) | (m1 > 15) | (m2 > 15);          // escaped values only cost extra bits in ESC regions
 #if LHIP_NL == 1
 #pragma unroll
-    for (int j = 0; j < NPL; j++) {
+    for (int j = 0; j < NR; j++) {
         const int p = 2 * (lane + LHIP_NL * j);
         if (p < i) {
             const int r = (p >= a1) + (p >= a2);
@@ -939,7 +966,7 @@ LHIP_DEV int q_noquant_count_bits(const Tables& T, GI& g, const int16_t* ix, int
     // same work in stages (all descriptors, all gathers, all sums), which keeps fifteen more values live
     if (any_esc) {
 #pragma unroll
-        for (int j = 0; j < NPL; j++) {
+        for (int j = 0; j < NR; j++) {
             if (rj[j] < 3) {
                 const int r = rj[j];
                 const uint64_t d = *(const uint64_t*)L.rdesc[r];
@@ -956,7 +983,7 @@ LHIP_DEV int q_noquant_count_bits(const Tables& T, GI& g, const int16_t* ix, int
     } else {
         // no region holds a value above 15 (three calls in four at stereo 128 kbps): nothing to clamp, no escapes to count
 #pragma unroll
-        for (int j = 0; j < NPL; j++) {
+        for (int j = 0; j < NR; j++) {
             if (rj[j] < 3) {
                 const int r = rj[j];
                 const uint64_t d = *(const uint64_t*)L.rdesc[r];
@@ -1018,6 +1045,7 @@ struct PrevNoise { int gain, sfb_count1; };
 // count_bits (Takehiro.js:630-660)
 // `use_pn` selects the prev_noise cache; pn is passed by reference with a flag (never as a nullable pointer to a
 // local: a select between private addresses is a per-lane value for the compiler and makes the control flow divergent)
+template <int NR>
 LHIP_DEV int q_count_bits(const Tables& T, GI& g, const int32_t* scalefac, int16_t* ix, int use_pn, PrevNoise& pn, int* asg, int lane, QuantLds& L, const QuantTabs& Q) {
     *asg = 0;
     {   // Takehiro.js:635-638: `xrpow_max > IXMAX_VAL / IPOW20(gain)`.  The division is only needed when the product is
@@ -1028,16 +1056,26 @@ LHIP_DEV int q_count_bits(const Tables& T, GI& g, const int32_t* scalefac, int16
             if (g.xrpow_max > w) return LARGE_BITS;
         }
     }
-    int vx[NPL], vy[NPL];
-    { PH_BEGIN(); q_quantize(T, g, scalefac, ix, use_pn, use_pn ? pn.gain : 0, use_pn ? pn.sfb_count1 : 0, vx, vy, lane, L, Q); PH_END(L, PH_QUANTIZE); }
+    int vx[NR], vy[NR];
+    { PH_BEGIN(); q_quantize<NR>(T, g, scalefac, ix, use_pn, use_pn ? pn.gain : 0, use_pn ? pn.sfb_count1 : 0, vx, vy, lane, L, Q); PH_END(L, PH_QUANTIZE); }
     int cnt1 = pn.sfb_count1;
     PH_BEGIN();
     int amask = 0;
-    const int r = q_noquant_count_bits(T, g, ix, vx, vy, use_pn, &cnt1, &amask, lane, L, Q);
+    const int r = q_noquant_count_bits<NR>(T, g, ix, vx, vy, use_pn, &cnt1, &amask, lane, L, Q);
     *asg = pack_cond_fields(g, amask);
     if (use_pn) pn.sfb_count1 = cnt1;
     PH_END(L, PH_COUNT);
     return r;
+}
+// one evaluation with the round count the granule-channel needs, chosen by one scalar branch: each form keeps its own interleaved schedule,
+// and the short one holds fewer live registers.  SKIP == 0 (the latency kernels): the full form only, not one instruction more in their loop
+template <int SKIP>
+LHIP_DEV int q_count_bits_rounds(const Tables& T, GI& g, const int32_t* scalefac, int16_t* ix, int use_pn, PrevNoise& pn, int* asg, int lane, QuantLds& L, const QuantTabs& Q) {
+    if constexpr (SKIP != 0) {
+        if (g.tail0) { LHIP_ROUND_COUNT(head); return q_count_bits<NPL_HEAD>(T, g, scalefac, ix, use_pn, pn, asg, lane, L, Q); }
+    }
+    LHIP_ROUND_COUNT(full);
+    return q_count_bits<NPL>(T, g, scalefac, ix, use_pn, pn, asg, lane, L, Q);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1356,7 +1394,7 @@ LHIP_DEV void q_count_helper(const Tables& T, CountShare& cs, const QuantLds& Lo
 #ifdef LHIP_PHASE_PROF
         const unsigned long long hp_start_ = __builtin_amdgcn_s_memtime();
 #endif
-        const int bits = uni(q_noquant_count_bits(T, g, Lo.ixw, vx, vy, 1, &cnt1, &amask, lane, L, Q));
+        const int bits = uni(q_noquant_count_bits<NPL>(T, g, Lo.ixw, vx, vy, 1, &cnt1, &amask, lane, L, Q));
 #ifdef LHIP_PHASE_PROF
         const unsigned long long hp_end_ = __builtin_amdgcn_s_memtime();
 #endif
@@ -1393,7 +1431,7 @@ LHIP_DEV int q_count_bits_piped(const Tables& T, GI& g, const int32_t* scalefac,
     }
     {
         int vx[NPL], vy[NPL];
-        PH_BEGIN(); q_quantize(T, g, scalefac, ix, 1, pn.gain, pn.sfb_count1, vx, vy, lane, L, Q); PH_END(L, PH_QUANTIZE);
+        PH_BEGIN(); q_quantize<NPL>(T, g, scalefac, ix, 1, pn.gain, pn.sfb_count1, vx, vy, lane, L, Q); PH_END(L, PH_QUANTIZE);
         (void)vx; (void)vy;                          // the helper reads the pairs back from LDS
     }
 #ifdef LHIP_PHASE_PROF
@@ -1529,20 +1567,21 @@ LHIP_DEV int q_loop_break(const GI& g, const int32_t* scalefac, int lane, QuantL
 // multiply xrpow of the flagged bands (bit sfb of m_amp) by `amp`, tracking xrpow_max.  Branch-free: an unflagged pair is
 // multiplied by 1.0 (exact through the f32 -> f64 -> f32 round trip) and takes part in the maximum like the flagged ones --
 // xrpow_max already bounds every unflagged line, so the update `if (max > xrpow_max)` sees the same verdict.
-LHIP_DEV void q_amplify_flagged(GI& g, double amp, uint64_t m_amp, int lane, QuantLds& L, const QuantTabs& Q) {
+template <int NR>
+LHIP_DEV void q_amplify_rounds(GI& g, double amp, uint64_t m_amp, int lane, QuantLds& L, const QuantTabs& Q) {
     lane = fresh_lane(lane);
     float m = 0.f;
     const uint8_t* l2s = line2sfb(Q, g.block_type);
     struct F2 { float x, y; };
-    F2 xx[NPL]; int bnd[NPL];
+    F2 xx[NR]; int bnd[NR];
 #pragma unroll
-    for (int j = 0; j < NPL; j++) {                             // pairs never straddle a band
+    for (int j = 0; j < NR; j++) {                             // pairs never straddle a band
         const int p = 2 * (lane + LHIP_NL * j);
         xx[j].x = 0.f; xx[j].y = 0.f; bnd[j] = 0;
         if (p < 576) { xx[j] = *(const F2*)(L.xrpow + p); bnd[j] = l2s[p]; }
     }
 #pragma unroll
-    for (int j = 0; j < NPL; j++) {
+    for (int j = 0; j < NR; j++) {
         const int p = 2 * (lane + LHIP_NL * j);
         const double a = ((m_amp >> bnd[j]) & 1) ? amp : 1.0;
         xx[j].x = (float)((double)xx[j].x * a); xx[j].y = (float)((double)xx[j].y * a);
@@ -1553,12 +1592,21 @@ LHIP_DEV void q_amplify_flagged(GI& g, double amp, uint64_t m_amp, int lane, Qua
     if ((double)m > g.xrpow_max) g.xrpow_max = m;
     wave_sync();
 }
+// (zero lines stay zero under any amplification and add nothing to the maximum)
+template <int SKIP>
+LHIP_DEV void q_amplify_flagged(GI& g, double amp, uint64_t m_amp, int lane, QuantLds& L, const QuantTabs& Q) {
+    if constexpr (SKIP != 0) {
+        if (g.tail0) { q_amplify_rounds<NPL_HEAD>(g, amp, m_amp, lane, L, Q); return; }
+    }
+    q_amplify_rounds<NPL>(g, amp, m_amp, lane, L, Q);
+}
 
 // amp_scalefac_bands (Quantize.js:597-669) + loop_break (453-460) + the scalefactor statistics scale_bitcount starts with
 // (Takehiro.js:980-1005), in ONE pass over the bands: the amplification decision, the incremented scalefactor, "is any band
 // still at zero" and, for MPEG-1 long blocks, "could the pretab be subtracted" / the two range maxima all look at the same
 // scalefac[sfb].  *all_nonzero = loop_break's verdict; *pre_bad / *m12 feed q_scale_bitcount_from (values BEFORE a preflag
 // subtraction, which that function applies itself when it is due).
+template <int SKIP>
 LHIP_DEV void q_amp_scalefac_bands(const Tables& T, GI& g, int32_t* scalefac, int* all_nonzero, int* pre_bad, int* m12_out,
                                    int lane, QuantLds& L, const QuantTabs& Q) {
     lane = fresh_lane(lane);
@@ -1602,7 +1650,7 @@ LHIP_DEV void q_amp_scalefac_bands(const Tables& T, GI& g, int32_t* scalefac, in
         const int r = wave_or(m12 | (z << 16) | (bad << 17));
         *m12_out = r & 0xffff; *all_nonzero = !((r >> 16) & 1); *pre_bad = (r >> 17) & 1;
     }
-    { unsigned long long tt_ = PH_NOW(); (void)tt_; q_amplify_flagged(g, ifqstep34, m_amp, lane, L, Q); PH_MARKB(L, PH_B_TRIG, tt_); }
+    { unsigned long long tt_ = PH_NOW(); (void)tt_; q_amplify_flagged<SKIP>(g, ifqstep34, m_amp, lane, L, Q); PH_MARKB(L, PH_B_TRIG, tt_); }
 }
 
 // scale_bitcount (MPEG-1) continuing from the statistics of q_amp_scalefac_bands: pre_bad = some band 11..20 is below its
@@ -1631,6 +1679,7 @@ LHIP_DEV int q_scale_bitcount_from(const QuantTabs& Q, GI& g, int32_t* scalefac,
     return g.part2_length == LARGE_BITS;
 }
 
+template <int SKIP>
 LHIP_DEV void q_inc_scalefac_scale(const Tables& T, GI& g, int32_t* scalefac, int lane, QuantLds& L, const QuantTabs& Q) {
     lane = fresh_lane(lane);
     uint64_t m_amp = 0;
@@ -1644,7 +1693,7 @@ LHIP_DEV void q_inc_scalefac_scale(const Tables& T, GI& g, int32_t* scalefac, in
     wave_sync();
     g.preflag = 0;
     g.scalefac_scale = 1;
-    q_amplify_flagged(g, 1.29683955465100964055, m_amp, lane, L, Q);
+    q_amplify_flagged<SKIP>(g, 1.29683955465100964055, m_amp, lane, L, Q);
 }
 
 // inc_subblock_gain (Quantize.js:705-778); returns 1 on failure.  Short blocks only (sfb_lmax == 0).
@@ -1696,11 +1745,12 @@ LHIP_DEV int q_inc_subblock_gain(const Tables& T, GI& g, int32_t* scalefac, int 
 }
 
 // balance_noise (Quantize.js:793-846); returns 1 to continue the outer loop
+template <int SKIP>
 LHIP_DEV int q_balance_noise(const Tables& T, GI& g, int32_t* scalefac, int lane, QuantLds& L, const QuantTabs& Q) {
     lane = fresh_lane(lane);
     unsigned long long tb_ = PH_NOW(); (void)tb_;
     int all_nonzero, pre_bad, m12;
-    q_amp_scalefac_bands(T, g, scalefac, &all_nonzero, &pre_bad, &m12, lane, L, Q);
+    q_amp_scalefac_bands<SKIP>(T, g, scalefac, &all_nonzero, &pre_bad, &m12, lane, L, Q);
     PH_MARKB(L, PH_B_AMP, tb_);
     int status = all_nonzero;                                  // loop_break (Quantize.js:453-460)
     if (status) return 0;
@@ -1709,7 +1759,7 @@ LHIP_DEV int q_balance_noise(const Tables& T, GI& g, int32_t* scalefac, int lane
     if (!status) return 1;
     if (T.noise_shaping > 1) {
         if (0 == g.scalefac_scale) {
-            q_inc_scalefac_scale(T, g, scalefac, lane, L, Q);
+            q_inc_scalefac_scale<SKIP>(T, g, scalefac, lane, L, Q);
             status = 0;
         } else if (g.block_type == SHORT_TYPE && T.subblock_gain > 0) {
             status = (q_inc_subblock_gain(T, g, scalefac, lane, L, Q) || q_loop_break(g, scalefac, lane, L, Q));
@@ -1792,6 +1842,7 @@ inline SearchStats& search_stats() { static SearchStats t; return t; }
 #else
 #define LHIP_SS(...) do { } while (0)
 #endif
+template <int SKIP = 0>
 LHIP_DEV void q_outer_loop(const Tables& T, GI& g, int targ_bits, int bs_start, int bs_step, int* bs_gain_out,
                            int16_t* kept, GrSide* rec, uint32_t* dig, int64_t dn, int lane, QuantLds& L, const QuantTabs& Q, CountShare* cs = nullptr) {
     lane = fresh_lane(lane);
@@ -1830,7 +1881,7 @@ LHIP_DEV void q_outer_loop(const Tables& T, GI& g, int targ_bits, int bs_start, 
         if (cs != nullptr && st >= ST_A) nBits = q_count_bits_piped(T, w, L.sfw, L.ixw, pn, &asg, *cs, &ni, &nc, best.over_count == 0, &spec, lane, L, Q);
         else
 #endif
-        nBits = q_count_bits(T, w, L.sfw, L.ixw, st >= ST_A, pn, &asg, lane, L, Q);   // the only call site (but for the two-wave form above)
+        nBits = q_count_bits_rounds<SKIP>(T, w, L.sfw, L.ixw, st >= ST_A, pn, &asg, lane, L, Q);   // the only call site (but for the two-wave form above)
         LHIP_SS(ss_.evals++; if (st == ST_BS) ss_nbs++; else if (st == ST_BSUP) ss_nup++;
                 if (st >= ST_A && ss_run > 0) { ss_.run_steps++; if (ss_moved) ss_.run_steps_cnt1_moved++; if (cnt1_seen > 0) ss_.run_steps_zo++; });
         // memo of the bin search: collected in LDS and written to the side record in one burst when the search ends (a global
@@ -1925,7 +1976,7 @@ LHIP_DEV void q_outer_loop(const Tables& T, GI& g, int targ_bits, int bs_start, 
         if (!first && !((w.global_gain + w.scalefac_scale) < 255)) break;
         first = 0;
         int bal_;
-        { PH_BEGIN(); bal_ = q_balance_noise(T, w, L.sfw, lane, L, Q); PH_END(L, PH_BALANCE); }       // the only call site
+        { PH_BEGIN(); bal_ = q_balance_noise<SKIP>(T, w, L.sfw, lane, L, Q); PH_END(L, PH_BALANCE); }       // the only call site
         if (!bal_) break;
         maxggain = (w.scalefac_scale != 0) ? 254 : 255;
         huff_bits = targ_bits - w.part2_length;
@@ -2458,11 +2509,18 @@ LHIP_DEV int targ_bits_for(const Tables& T, int mean_bits, int gr, int ResvSize,
 // (valid if `active`) and the block type.
 struct UnitOut { int bits; Seed next; int block_type; int active; };
 // Inlined at every call site: behind a call (one copy of the code for kb_quant's, the owner's and the helper's site) g_quant was a third slower -- spills around the call.
+// SKIP == 1 (the batch kernels): a granule-channel whose lines 512..575 are all zero runs its per-pair rounds without the last one (GI::tail0)
+template <int SKIP = 0>
 LHIP_DEV UnitOut q_unit(const Tables& T, const PowBase& pb10, const Workspace& W, int C, int Cp, int fidx, int gslot, int gr, int ch, int mode_ext,
                         double ath_adjust, int targ_ch, Seed used, int gr0_bt, int lane, QuantLds& L, const QuantTabs& Q, CountShare* cs = nullptr) {
     lane = lane_anew(lane);        // (here and below: lane-derived LDS / HBM addresses are formed where they are used, not parked in scratch across the search)
     UnitOut u; u.next = used;
     GI g;
+#if defined(LHIP_HOSTSIM)
+    // simulations only: what the unit before left in the words 256..287 of the working spectrum is made visible -- at 44.1 / 48 kHz those lines lie in the
+    // last band, beyond big_values and count1, where a stale value of ordinary size changes no byte; a unit that runs without the last round must zero them
+    if (SKIP) { for (int i = 256 + lane; i < 288; i += LHIP_NL) ((uint32_t*)L.ixw)[i] = 0x1fff1fffu; wave_sync(); }
+#endif
     const int bt = W.blocktype[(int64_t)gslot * C + ch];
     const double masking_lower = (bt != SHORT_TYPE) ? T.masking_lower_long : T.masking_lower_short;
     const float* ratio = W.E + ((int64_t)(gslot - 1) * Cp + ch + mode_ext) * E_STRIDE;   // thresholds of the previous psy call (mid / side: channels 2, 3)
@@ -2470,9 +2528,14 @@ LHIP_DEV UnitOut q_unit(const Tables& T, const PowBase& pb10, const Workspace& W
     int active = 0, bs_gain = 0;
     if (q_init_xrpow(g, lane, L, Q)) {
         active = 1;
-        { PH_BEGIN(); q_calc_xmin(T, ath_adjust, masking_lower, ratio, g, lane, L, Q); PH_END(L, PH_XMIN); }
+        { PH_BEGIN(); q_calc_xmin(T, ath_adjust, masking_lower, ratio, g, lane, L, Q, SKIP); PH_END(L, PH_XMIN); }
+        if constexpr (SKIP != 0) {
+            // L.ixw outlives a granule-channel: no evaluation of this search writes the words 256..287, so they must not keep what the
+            // unit before left there.  `kept`, the published spectrum and everything read after the search cover all 576 lines as before.
+            if (g.tail0) { for (int i = 256 + lane; i < 288; i += LHIP_NL) ((uint32_t*)L.ixw)[i] = 0u; wave_sync(); }
+        }
         int16_t* kept = cs ? cs->kept : W.l3 + (((int64_t)fidx * 2 + gr) * C + ch) * 576;
-        { PH_BEGIN(); q_outer_loop(T, g, targ_ch, used.start, used.step, &bs_gain, kept, W.side + ((int64_t)fidx * 2 + gr) * C + ch, W.vdig + ((int64_t)fidx * 2 + gr) * C + ch, W.vdig_n, lane, L, Q, cs); PH_END(L, PH_XRPOW); }   // (profiling builds: the whole search in the otherwise unused slot)
+        { PH_BEGIN(); q_outer_loop<SKIP>(T, g, targ_ch, used.start, used.step, &bs_gain, kept, W.side + ((int64_t)fidx * 2 + gr) * C + ch, W.vdig + ((int64_t)fidx * 2 + gr) * C + ch, W.vdig_n, lane, L, Q, cs); PH_END(L, PH_XRPOW); }   // (profiling builds: the whole search in the otherwise unused slot)
         uni_gi(g); bs_gain = uni(bs_gain);
         lane = lane_anew(lane);
         wave_sync();                                    // the kept spectrum was written by other lanes of this wave
@@ -2518,7 +2581,7 @@ LHIP_DEV UnitOut q_unit(const Tables& T, const PowBase& pb10, const Workspace& W
         out->active = active; out->bs_start = used.start; out->bs_step_in = used.step; out->bs_gain = bs_gain;
         W.vdig[((int64_t)fidx * 2 + gr) * C + ch] = vd_head(active, used.start, used.step, bs_gain);      // digest word VD_HEAD
         out->targ_bits = targ_ch;
-        out->mode_ext = mode_ext;
+        out->mode_ext = uni_here(mode_ext);      // (formed here: hoisted to the frame's start as a vector copy, it would be the one value the search spills)
         out->scfsi = scfsi[0] | (scfsi[1] << 1) | (scfsi[2] << 2) | (scfsi[3] << 3);
     }
     LHIP_LANE_ONCE(i, 0, SFBMAX) out->scalefac[i] = L.sfb[i];
@@ -2543,7 +2606,7 @@ LHIP_DEV UnitOut q_unit(const Tables& T, const PowBase& pb10, const Workspace& W
 // granule to exchange the bits they used (ResvSize feeds the next granule's budget) through `mbox` in LDS.
 // RESV == 1: the bit-reservoir extension (Tables::disable_reservoir == 0) -- a separate instantiation, so that the usual path carries none
 // of its state (the entropies, the reservoir record) through the frame
-template <int PAIR = 0, int RESV = 0>
+template <int PAIR = 0, int RESV = 0, int SKIP = 0>
 LHIP_DEV void kb_quant(const Tables& T, const PowBase& pb10, const Workspace& W, const StreamDesc* SD, int fslot,
                        int chain, int lane, QuantLds& L, const QuantTabs& Q, int my_ch = -1, int* mbox = nullptr, const ResvState* rvp = nullptr,
                        int* hint = nullptr, CountShare* cs = nullptr, const int* later_granules_ready = nullptr) {
@@ -2633,8 +2696,8 @@ LHIP_DEV void kb_quant(const Tables& T, const PowBase& pb10, const Workspace& W,
         const int targ0 = uni(targ[0]), targ1 = uni(targ[1]);
         for (int ch = 0; ch < C; ch++) {
             if (PAIR && ch != my_ch) continue;
-            const UnitOut u = q_unit(T, pb10, W, C, Cp, fidx, gslot, gr, ch, mode_ext, ath_adjust, ch == 0 ? targ0 : targ1, ch == 0 ? seed0 : seed1,
-                                     ch == 0 ? gr0_bt0 : gr0_bt1, lane, L, Q, cs);
+            const UnitOut u = q_unit<SKIP>(T, pb10, W, C, Cp, fidx, gslot, gr, ch, mode_ext, ath_adjust, ch == 0 ? targ0 : targ1, ch == 0 ? seed0 : seed1,
+                                           ch == 0 ? gr0_bt0 : gr0_bt1, lane, L, Q, cs);
             if (u.active) { if (ch == 0) seed0 = u.next; else seed1 = u.next; }
             if (!PAIR) ResvSize = uni(ResvSize - u.bits);
             else if (lane == 0) mbox[2 * gr + ch] = u.bits;
@@ -2680,6 +2743,7 @@ LHIP_DEV void kb_quant(const Tables& T, const PowBase& pb10, const Workspace& W,
 // The search only asks for count_bits(gain) with all-zero scalefactors; the speculative pass left a memo of every
 // such evaluation (GrSide::bs_tab), so most replays are pure scalar look-ups and the spectrum is only re-quantized
 // on a miss.
+template <int SKIP>
 LHIP_DEV void kb_validate(const Tables& T, const PowBase& pb10, const Workspace& W, const StreamDesc* SD, int fslot,
                           int lane, QuantLds& L, const QuantTabs& Q) {
     const int C = T.channels_out;
@@ -2739,12 +2803,13 @@ LHIP_DEV void kb_validate(const Tables& T, const PowBase& pb10, const Workspace&
                             for (int i = lane; i < 576; i += LHIP_NL) if (!((double)L.xr[i] == 0)) t = i;
                             t = wave_max(t);
                             g.max_nonzero_coeff = (t >= 575) ? 575 : t + 1;
-                        }
+                            if (SKIP) g.tail0 = t < 512;
+                        } else if (SKIP) g.tail0 = q_tail_is_zero(lane, L);         // as q_calc_xmin sets it (only the bit count is used here: stale words 256..287 of L.ixw are never read)
                         q_set_firstcut(g, lane, L);
                         inited = 1;
                     }
                     g.global_gain = gain;
-                    nBits = q_count_bits(T, g, L.sfb, L.ixw, 0, pn_none, &asg, lane, L, Q);
+                    nBits = q_count_bits_rounds<SKIP>(T, g, L.sfb, L.ixw, 0, pn_none, &asg, lane, L, Q);
                 }
                 nBits = uni(nBits);
                 cstate = apply_cond_fields(cstate, uni(asg));

@@ -32,6 +32,7 @@ inline TailStats& tail_stats() { static TailStats t; return t; }
 // (the workgroup-scope signalling primitives wg_cas / wg_load / wg_store / wg_idle / wg_acquire and LHIP_SPIN_GUARD live in lhip_wave.h)
 
 // kb_quant for the persistent kernel's speculative pass (chain == 0, no reservoir) with the second channel of every granule on offer
+template <int SKIP>
 LHIP_DEV void kb_quant_th(const Tables& T, const PowBase& pb10, const Workspace& W, const StreamDesc* SD, int fslot, int lane, QuantLds& L,
                           const QuantTabs& Q, int* hint, TailShare& TS, int wv) {
     lane = lane_anew(lane);
@@ -91,8 +92,8 @@ LHIP_DEV void kb_quant_th(const Tables& T, const PowBase& pb10, const Workspace&
                 continue;
             }
             if (ch == 1) LHIP_TAIL_COUNT(withdrawn);   // nobody took it: the serial order
-            const UnitOut u = q_unit(T, pb10, W, C, Cp, fidx, gslot, gr, ch, mode_ext, ath_adjust, ch == 0 ? targ0 : targ1, ch == 0 ? seed0 : seed1,
-                                     ch == 0 ? gr0_bt0 : gr0_bt1, lane, L, Q);
+            const UnitOut u = q_unit<SKIP>(T, pb10, W, C, Cp, fidx, gslot, gr, ch, mode_ext, ath_adjust, ch == 0 ? targ0 : targ1, ch == 0 ? seed0 : seed1,
+                                        ch == 0 ? gr0_bt0 : gr0_bt1, lane, L, Q);
             if (u.active) { if (ch == 0) seed0 = u.next; else seed1 = u.next; }
             ResvSize = uni(ResvSize - u.bits);
             if (gr == 0) { if (ch == 0) gr0_bt0 = u.block_type; else gr0_bt1 = u.block_type; }
@@ -105,6 +106,7 @@ LHIP_DEV void kb_quant_th(const Tables& T, const PowBase& pb10, const Workspace&
 }
 
 // a wave that has found the dispenser empty: take open offers of the workgroup until no wave can draw a frame any more
+template <int SKIP>
 LHIP_DEV void tail_help(const Tables& T, const PowBase& pb10, const Workspace& W, const StreamDesc* SD, int lane, QuantLds* Lall, int wv, int nwaves,
                         const QuantTabs& Q, TailShare& TS) {
     lane = lane_anew(lane);
@@ -132,7 +134,7 @@ LHIP_DEV void tail_help(const Tables& T, const PowBase& pb10, const Workspace& W
             q_ath_pseudo(T, pb10, ath_adjust, lane, L, Q);
             if (gr == 1) { LHIP_LANE_ONCE(i, 0, (SFBMAX) + 1) L.sf_gr0[1][i] = Lall[w].sf_gr0[1][i]; }
             wave_sync();
-            const UnitOut u = q_unit(T, pb10, W, C, Cp, fidx, gslot, gr, 1, mode_ext, ath_adjust, targ, seed, gr0_bt, lane, L, Q);
+            const UnitOut u = q_unit<SKIP>(T, pb10, W, C, Cp, fidx, gslot, gr, 1, mode_ext, ath_adjust, targ, seed, gr0_bt, lane, L, Q);
             if (gr == 0) { LHIP_LANE_ONCE(i, 0, (SFBMAX) + 1) Lall[w].sf_gr0[1][i] = L.sf_gr0[1][i]; }
             if (lane == 0) { o.bits = u.bits; o.active = u.active; o.next_start = u.next.start; o.next_step = u.next.step; o.block_type = u.block_type; }
             wg_store(&o.state, 3, lane);

@@ -677,6 +677,12 @@ int lhip_debug_last_paths(uint32_t* mask) {
 }
 
 int64_t lhip_debug_read(int what, void* dst, size_t cap) {
+#ifdef LHIP_HOSTSIM
+    if (what == 10) {                                   // evaluations so far with the short / the full round count (RoundStats, k_quant.h)
+        const int64_t v[2] = {(int64_t)__atomic_load_n(&round_stats().head, __ATOMIC_RELAXED), (int64_t)__atomic_load_n(&round_stats().full, __ATOMIC_RELAXED)};
+        const size_t n = cap < sizeof v ? cap : sizeof v; memcpy(dst, v, n); return (int64_t)n;
+    }
+#endif
 #ifdef LHIP_PHASE_PROF
     if (what == 9) { const size_t n = cap < sizeof g_call_prof ? cap : sizeof g_call_prof; memcpy(dst, g_call_prof, n); return (int64_t)n; }
 #endif

@@ -91,7 +91,10 @@ struct QArgs { Tables T; PowBase pb; Workspace W; const StreamDesc* SD; int chai
 #else
 #define LHIP_QUANT_BOUNDS __launch_bounds__(64 * QWAVES, LHIP_QOCC)
 #endif
-template <int RESV> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_unused) {
+// SKIP: the batch kernels exist in two forms -- with the search's dead last round of pairs skipped where the granule-channel's spectrum allows it (GI::tail0,
+// k_quant.h), and without any of that code: the host launches the second where the configuration's lowpass leaves lines above 512 in every long block (320 kbps),
+// which would only carry the first form's larger code (measured: + 1 % of such a step)
+template <int RESV, int SKIP> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_unused) {
     __shared__ QuantTabs Q;
     __shared__ QuantLds L[QWAVES];
     __shared__ TailShare TS;
@@ -117,12 +120,12 @@ template <int RESV> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_unused) {
         if (fslot >= A->nfs) break;
         // the speculative pass (chain == 0): the frame program with the second channel of every granule on offer to the workgroup's idle waves
         // (k_quant_tail.h); with the reservoir the frames are a chain and this kernel is not launched (g_resv_stream)
-        if constexpr (!RESV) kb_quant_th(A->T, A->pb, A->W, A->SD, fslot, threadIdx.x & 63, L[wv], Q, hint, TS, wv);
-        else kb_quant<0, RESV>(A->T, A->pb, A->W, A->SD, fslot, A->chain, threadIdx.x & 63, L[wv], Q, -1, nullptr, nullptr, nullptr);
+        if constexpr (!RESV) kb_quant_th<SKIP>(A->T, A->pb, A->W, A->SD, fslot, threadIdx.x & 63, L[wv], Q, hint, TS, wv);
+        else kb_quant<0, RESV, SKIP>(A->T, A->pb, A->W, A->SD, fslot, A->chain, threadIdx.x & 63, L[wv], Q, -1, nullptr, nullptr, nullptr);
         hint[0] = __builtin_amdgcn_readfirstlane(hint[0]); hint[1] = __builtin_amdgcn_readfirstlane(hint[1]); hint[2] = __builtin_amdgcn_readfirstlane(hint[2]);
     }
     // the dispenser is empty: stay and take the second channels that this workgroup's waves still have ahead of them
-    if (tail_help_on) tail_help(A->T, A->pb, A->W, A->SD, threadIdx.x & 63, L, wv, QWAVES, Q, TS);
+    if (tail_help_on) tail_help<SKIP>(A->T, A->pb, A->W, A->SD, threadIdx.x & 63, L, wv, QWAVES, Q, TS);
 #ifdef LHIP_PHASE_PROF
     atomicAdd((unsigned long long*)A->W.prof + (threadIdx.x & 63), (unsigned long long)L[wv].prof[threadIdx.x & 63]);
 #endif
@@ -136,7 +139,7 @@ template <int RESV> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_unused) {
 // Latency path for small stereo batches: one workgroup of two waves per frame, one wave per channel (kb_quant<1>).  A single
 // frame is one wave's serially dependent search; with fewer frames than SIMDs the chip is idle anyway, so the two channels
 // of a granule -- independent given the granule's bit budget -- run side by side.
-template <int RESV> __global__ __launch_bounds__(128, LHIP_QOCC) void g_quant_pair(QArgs a_unused) {
+template <int RESV, int SKIP> __global__ __launch_bounds__(128, LHIP_QOCC) void g_quant_pair(QArgs a_unused) {
     __shared__ QuantTabs Q;
     __shared__ QuantLds L[2];
     __shared__ int mbox[4];
@@ -144,7 +147,7 @@ template <int RESV> __global__ __launch_bounds__(128, LHIP_QOCC) void g_quant_pa
     q_copy_tabs(A->T, Q, threadIdx.x, 128);
     __syncthreads();
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    kb_quant<1, RESV>(A->T, A->pb, A->W, A->SD, blockIdx.x, A->chain, threadIdx.x & 63, L[wv], Q, wv, mbox);
+    kb_quant<1, RESV, SKIP>(A->T, A->pb, A->W, A->SD, blockIdx.x, A->chain, threadIdx.x & 63, L[wv], Q, wv, mbox);
 }
 __global__ __launch_bounds__(256) void g_validate_fast(Tables T, Workspace W, const StreamDesc* SD, int nfs) {
     __shared__ ValidateShare S;
@@ -183,7 +186,7 @@ LHIP_DEV void grid_barrier(int32_t* bar, int nblocks) {
 #ifndef LHIP_FIXUP_OCC
 #define LHIP_FIXUP_OCC 4
 #endif
-__global__ __launch_bounds__(64 * QWAVES, LHIP_FIXUP_OCC) void g_fixup(QArgs a_unused) {
+template <int SKIP> __global__ __launch_bounds__(64 * QWAVES, LHIP_FIXUP_OCC) void g_fixup(QArgs a_unused) {
     __shared__ QuantTabs Q;
     __shared__ QuantLds L[QWAVES];
     const QArgs* A = (const QArgs*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -216,7 +219,7 @@ __global__ __launch_bounds__(64 * QWAVES, LHIP_FIXUP_OCC) void g_fixup(QArgs a_u
         if (nslow > 0) {                                                      // frames whose replay asked for a gain never evaluated
             if (!tabs) { q_copy_tabs(A->T, Q, threadIdx.x, nthr); __syncthreads(); tabs = true; }
             for (int i = gw; i < nslow; i += nw)
-                kb_validate(A->T, A->pb, W, A->SD, __builtin_amdgcn_readfirstlane(W.slow_list[i]), lane, L[wv], Q);
+                kb_validate<SKIP>(A->T, A->pb, W, A->SD, __builtin_amdgcn_readfirstlane(W.slow_list[i]), lane, L[wv], Q);
             grid_barrier(base + FX_BAR, nblocks);
         }
         const int nflag = __builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr + FX_NFLAG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -241,7 +244,7 @@ __global__ __launch_bounds__(64 * QWAVES, LHIP_FIXUP_OCC) void g_fixup(QArgs a_u
                 const int l = (int)__builtin_ctzll(m);
                 m &= m - 1;
                 const int fr = b0 + nw * l;
-                kb_quant(A->T, A->pb, W, A->SD, fr, 1, lane, L[wv], Q);
+                kb_quant<0, 0, SKIP>(A->T, A->pb, W, A->SD, fr, 1, lane, L[wv], Q);
                 if (lane == 0) {                                              // its successor (same stream) is what the next pass re-checks
                     const StreamDesc* sd = A->SD + W.fslot_stream[fr];
                     const int k = fr - sd->fslot0 - 1;

@@ -137,16 +137,28 @@ template <int N> LHIP_DEV void q_floor_prod(const float (&xa)[N], const float (&
 #ifdef LHIP_HOSTSIM
     for (int j = 0; j < N; j++) { ra[j] = (int)((double)xa[j] * (double)istep); rb[j] = (int)((double)xb[j] * (double)istep); }
 #else
-    static_assert(N == 5, "device form is written for 5 pairs per lane");
-    float a0, a1, a2, a3, a4, b0, b1, b2, b3, b4;
-    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\ts_nop 1\n\t"
-                 "v_mul_f32 %0, %10, %20\n\tv_mul_f32 %1, %11, %20\n\tv_mul_f32 %2, %12, %20\n\tv_mul_f32 %3, %13, %20\n\tv_mul_f32 %4, %14, %20\n\t"
-                 "v_mul_f32 %5, %15, %20\n\tv_mul_f32 %6, %16, %20\n\tv_mul_f32 %7, %17, %20\n\tv_mul_f32 %8, %18, %20\n\tv_mul_f32 %9, %19, %20\n\t"
-                 "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\ts_nop 1"
-                 : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3), "=&v"(b4)
-                 : "v"(xa[0]), "v"(xa[1]), "v"(xa[2]), "v"(xa[3]), "v"(xa[4]), "v"(xb[0]), "v"(xb[1]), "v"(xb[2]), "v"(xb[3]), "v"(xb[4]), "v"(istep));
-    ra[0] = (int)a0; ra[1] = (int)a1; ra[2] = (int)a2; ra[3] = (int)a3; ra[4] = (int)a4;
-    rb[0] = (int)b0; rb[1] = (int)b1; rb[2] = (int)b2; rb[3] = (int)b3; rb[4] = (int)b4;
+    static_assert(N == 5 || N == 4, "device forms are written for 5 and for 4 pairs per lane (NPL, NPL_HEAD)");
+    if constexpr (N == 5) {
+        float a0, a1, a2, a3, a4, b0, b1, b2, b3, b4;
+        asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\ts_nop 1\n\t"
+                     "v_mul_f32 %0, %10, %20\n\tv_mul_f32 %1, %11, %20\n\tv_mul_f32 %2, %12, %20\n\tv_mul_f32 %3, %13, %20\n\tv_mul_f32 %4, %14, %20\n\t"
+                     "v_mul_f32 %5, %15, %20\n\tv_mul_f32 %6, %16, %20\n\tv_mul_f32 %7, %17, %20\n\tv_mul_f32 %8, %18, %20\n\tv_mul_f32 %9, %19, %20\n\t"
+                     "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\ts_nop 1"
+                     : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3), "=&v"(b4)
+                     : "v"(xa[0]), "v"(xa[1]), "v"(xa[2]), "v"(xa[3]), "v"(xa[4]), "v"(xb[0]), "v"(xb[1]), "v"(xb[2]), "v"(xb[3]), "v"(xb[4]), "v"(istep));
+        ra[0] = (int)a0; ra[1] = (int)a1; ra[2] = (int)a2; ra[3] = (int)a3; ra[4] = (int)a4;
+        rb[0] = (int)b0; rb[1] = (int)b1; rb[2] = (int)b2; rb[3] = (int)b3; rb[4] = (int)b4;
+    } else {
+        float a0, a1, a2, a3, b0, b1, b2, b3;
+        asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\ts_nop 1\n\t"
+                     "v_mul_f32 %0, %8, %16\n\tv_mul_f32 %1, %9, %16\n\tv_mul_f32 %2, %10, %16\n\tv_mul_f32 %3, %11, %16\n\t"
+                     "v_mul_f32 %4, %12, %16\n\tv_mul_f32 %5, %13, %16\n\tv_mul_f32 %6, %14, %16\n\tv_mul_f32 %7, %15, %16\n\t"
+                     "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\ts_nop 1"
+                     : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3)
+                     : "v"(xa[0]), "v"(xa[1]), "v"(xa[2]), "v"(xa[3]), "v"(xb[0]), "v"(xb[1]), "v"(xb[2]), "v"(xb[3]), "v"(istep));
+        ra[0] = (int)a0; ra[1] = (int)a1; ra[2] = (int)a2; ra[3] = (int)a3;
+        rb[0] = (int)b0; rb[1] = (int)b1; rb[2] = (int)b2; rb[3] = (int)b3;
+    }
 #endif
 }
 template <int N> LHIP_DEV void q_floor_fma(const float (&xa)[N], const float (&xb)[N], float istep, const float (&ja)[N], const float (&jb)[N],
@@ -157,17 +169,30 @@ template <int N> LHIP_DEV void q_floor_fma(const float (&xa)[N], const float (&x
         vb[j] = (int)((double)xb[j] * (double)istep + (double)jb[j]);
     }
 #else
-    static_assert(N == 5, "device form is written for 5 pairs per lane");
-    float a0, a1, a2, a3, a4, b0, b1, b2, b3, b4;
-    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\ts_nop 1\n\t"
-                 "v_fma_f32 %0, %10, %20, %21\n\tv_fma_f32 %1, %11, %20, %22\n\tv_fma_f32 %2, %12, %20, %23\n\tv_fma_f32 %3, %13, %20, %24\n\tv_fma_f32 %4, %14, %20, %25\n\t"
-                 "v_fma_f32 %5, %15, %20, %26\n\tv_fma_f32 %6, %16, %20, %27\n\tv_fma_f32 %7, %17, %20, %28\n\tv_fma_f32 %8, %18, %20, %29\n\tv_fma_f32 %9, %19, %20, %30\n\t"
-                 "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\ts_nop 1"
-                 : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3), "=&v"(b4)
-                 : "v"(xa[0]), "v"(xa[1]), "v"(xa[2]), "v"(xa[3]), "v"(xa[4]), "v"(xb[0]), "v"(xb[1]), "v"(xb[2]), "v"(xb[3]), "v"(xb[4]), "v"(istep),
-                   "v"(ja[0]), "v"(ja[1]), "v"(ja[2]), "v"(ja[3]), "v"(ja[4]), "v"(jb[0]), "v"(jb[1]), "v"(jb[2]), "v"(jb[3]), "v"(jb[4]));
-    va[0] = (int)a0; va[1] = (int)a1; va[2] = (int)a2; va[3] = (int)a3; va[4] = (int)a4;
-    vb[0] = (int)b0; vb[1] = (int)b1; vb[2] = (int)b2; vb[3] = (int)b3; vb[4] = (int)b4;
+    static_assert(N == 5 || N == 4, "device forms are written for 5 and for 4 pairs per lane (NPL, NPL_HEAD)");
+    if constexpr (N == 5) {
+        float a0, a1, a2, a3, a4, b0, b1, b2, b3, b4;
+        asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\ts_nop 1\n\t"
+                     "v_fma_f32 %0, %10, %20, %21\n\tv_fma_f32 %1, %11, %20, %22\n\tv_fma_f32 %2, %12, %20, %23\n\tv_fma_f32 %3, %13, %20, %24\n\tv_fma_f32 %4, %14, %20, %25\n\t"
+                     "v_fma_f32 %5, %15, %20, %26\n\tv_fma_f32 %6, %16, %20, %27\n\tv_fma_f32 %7, %17, %20, %28\n\tv_fma_f32 %8, %18, %20, %29\n\tv_fma_f32 %9, %19, %20, %30\n\t"
+                     "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\ts_nop 1"
+                     : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3), "=&v"(b4)
+                     : "v"(xa[0]), "v"(xa[1]), "v"(xa[2]), "v"(xa[3]), "v"(xa[4]), "v"(xb[0]), "v"(xb[1]), "v"(xb[2]), "v"(xb[3]), "v"(xb[4]), "v"(istep),
+                       "v"(ja[0]), "v"(ja[1]), "v"(ja[2]), "v"(ja[3]), "v"(ja[4]), "v"(jb[0]), "v"(jb[1]), "v"(jb[2]), "v"(jb[3]), "v"(jb[4]));
+        va[0] = (int)a0; va[1] = (int)a1; va[2] = (int)a2; va[3] = (int)a3; va[4] = (int)a4;
+        vb[0] = (int)b0; vb[1] = (int)b1; vb[2] = (int)b2; vb[3] = (int)b3; vb[4] = (int)b4;
+    } else {
+        float a0, a1, a2, a3, b0, b1, b2, b3;
+        asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\ts_nop 1\n\t"
+                     "v_fma_f32 %0, %8, %16, %17\n\tv_fma_f32 %1, %9, %16, %18\n\tv_fma_f32 %2, %10, %16, %19\n\tv_fma_f32 %3, %11, %16, %20\n\t"
+                     "v_fma_f32 %4, %12, %16, %21\n\tv_fma_f32 %5, %13, %16, %22\n\tv_fma_f32 %6, %14, %16, %23\n\tv_fma_f32 %7, %15, %16, %24\n\t"
+                     "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\ts_nop 1"
+                     : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3)
+                     : "v"(xa[0]), "v"(xa[1]), "v"(xa[2]), "v"(xa[3]), "v"(xb[0]), "v"(xb[1]), "v"(xb[2]), "v"(xb[3]), "v"(istep),
+                       "v"(ja[0]), "v"(ja[1]), "v"(ja[2]), "v"(ja[3]), "v"(jb[0]), "v"(jb[1]), "v"(jb[2]), "v"(jb[3]));
+        va[0] = (int)a0; va[1] = (int)a1; va[2] = (int)a2; va[3] = (int)a3;
+        vb[0] = (int)b0; vb[1] = (int)b1; vb[2] = (int)b2; vb[3] = (int)b3;
+    }
 #endif
 }
 

@@ -102,7 +102,9 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
 #endif
     P.paths |= pair ? LHIP_PATH_QUANT_PAIR : LHIP_PATH_QUANT_PERSISTENT;
     { QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;
-      if (pair) LAUNCHB(KT_QUANT, g_quant_pair<0>, nfs, 128, st, qa); else LAUNCHB(KT_QUANT, g_quant<0>, qgrid, 64 * QWAVES, st, qa); }
+      // (which form is a matter of speed only: the skip itself is decided per granule-channel from its spectrum)
+      if (pair) { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant_pair<0, 1>), nfs, 128, st, qa); else LAUNCHB(KT_QUANT, (g_quant_pair<0, 0>), nfs, 128, st, qa); }
+      else { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant<0, 1>), qgrid, 64 * QWAVES, st, qa); else LAUNCHB(KT_QUANT, (g_quant<0, 0>), qgrid, 64 * QWAVES, st, qa); } }
     if (nfr > 0) {
         // validation of the seed chain + repair of the flagged frames, decided on the device (no host round trip in the pipeline)
         QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 1; qa.nfs = nfs; qa.ctr = 0;
@@ -112,13 +114,14 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
         int fgrid = (nfs + 63) / 64;
         if (ctx->fixup_wg_per_cu == 0) {      // once per context: how many of this build's g_fixup workgroups a CU really holds (a grid barrier needs them all resident)
             int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)g_fixup, 64 * QWAVES, 0) != hipSuccess || nb < 1) nb = 1;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)g_fixup<1>, 64 * QWAVES, 0) != hipSuccess || nb < 1) nb = 1;
             ctx->fixup_wg_per_cu = nb < LHIP_FIXUP_OCC / 2 ? nb : LHIP_FIXUP_OCC / 2;
         }
         if (fgrid > ctx->num_cus * ctx->fixup_wg_per_cu) fgrid = ctx->num_cus * ctx->fixup_wg_per_cu;
         if (fgrid < 1) fgrid = 1;
         P.paths |= fgrid == 1 ? LHIP_PATH_FIXUP_SINGLE : LHIP_PATH_FIXUP_COOP;
-        if (fgrid == 1) LAUNCHB(KT_VALIDATE, g_fixup, 1, 64 * QWAVES, st, qa);
+        const void* fixup_fn = ts.skip_tail ? (const void*)g_fixup<1> : (const void*)g_fixup<0>;
+        if (fgrid == 1) { if (ts.skip_tail) LAUNCHB(KT_VALIDATE, g_fixup<1>, 1, 64 * QWAVES, st, qa); else LAUNCHB(KT_VALIDATE, g_fixup<0>, 1, 64 * QWAVES, st, qa); }
         else {
             kt_begin(KT_VALIDATE, st);
             void* kargs[] = {(void*)&qa};
@@ -132,7 +135,7 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
                 if (!rt::event_record(ctx->ev_coop[0], st) || !rt::stream_wait_event(nullptr, ctx->ev_coop[0])) return false;
                 cst = nullptr;
             }
-            hipError_t e_ = hipLaunchCooperativeKernel((const void*)g_fixup, dim3(fgrid), dim3(64 * QWAVES), kargs, 0, cst);
+            hipError_t e_ = hipLaunchCooperativeKernel(fixup_fn, dim3(fgrid), dim3(64 * QWAVES), kargs, 0, cst);
             if (ctx->own_stream && e_ == hipSuccess) { if (!rt::event_record(ctx->ev_coop[1], nullptr) || !rt::stream_wait_event(st, ctx->ev_coop[1])) return false; }
             kt_end(st);
             TRACE_SYNC(g_fixup_cooperative, st);

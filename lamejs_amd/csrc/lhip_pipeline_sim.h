@@ -11,10 +11,10 @@
 #endif
 // QUANT_RUN: frame slot `b` once more through the quantization, as run_pipeline chose for the batch (`pair`)
 #ifdef LHIP_WAVESIM
-#define QUANT_RUN(chain_) do { if (pair) wsim::run_block(2, [&](int wave_, int lane_) { kb_quant<1, 0>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ2[wave_], QT, wave_, mbox); }); \
-                       else WAVE_RUN(kb_quant<0, 0>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ, QT)); } while (0)
+#define QUANT_RUN(chain_) do { if (pair) wsim::run_block(2, [&](int wave_, int lane_) { kb_quant<1, 0, 1>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ2[wave_], QT, wave_, mbox); }); \
+                       else WAVE_RUN(kb_quant<0, 0, 1>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ, QT)); } while (0)
 #else
-#define QUANT_RUN(chain_) WAVE_RUN(kb_quant<0, 0>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ, QT))
+#define QUANT_RUN(chain_) WAVE_RUN(kb_quant<0, 0, 1>(T, ts.pb10, W, dSD, b, chain_, lane_, LQ, QT))
 #endif
 // g_gain_stage and g_gain over a launch's descriptors (also lhip_debug_gain_windows)
 static void gain_sim_run(const Tables& T, const Workspace& W, const StreamDesc* SD, const StreamIO* IO, const GainDesc* D, int S, int stage_blocks, int waves) {
@@ -139,9 +139,9 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
                 if (lane_ == 0) f = ctr++;
                 f = wave_bcast(f, 0);
                 if (f >= nfs) break;
-                kb_quant_th(T, ts.pb10, W, dSD, f, lane_, LQ8[wave_], QT, hint, TS, wave_);
+                kb_quant_th<1>(T, ts.pb10, W, dSD, f, lane_, LQ8[wave_], QT, hint, TS, wave_);
             }
-            if (C == 2) tail_help(T, ts.pb10, W, dSD, lane_, LQ8, wave_, 8, QT, TS);
+            if (C == 2) tail_help<1>(T, ts.pb10, W, dSD, lane_, LQ8, wave_, 8, QT, TS);
         });
     } else
 #endif
@@ -153,18 +153,18 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
             if (pair) { QUANT_RUN(0); continue; }
             int hl[64][3];                                     // every lane fiber updates its own copy; they must agree (wave-uniform)
             for (int l = 0; l < 64; l++) for (int q = 0; q < 3; q++) hl[l][q] = hints[b % 3][q];
-            WAVE_RUN(kb_quant<0, 0>(T, ts.pb10, W, dSD, b, 0, lane_, LQ, QT, -1, nullptr, nullptr, hl[lane_]));
+            WAVE_RUN(kb_quant<0, 0, 1>(T, ts.pb10, W, dSD, b, 0, lane_, LQ, QT, -1, nullptr, nullptr, hl[lane_]));
             for (int l = 1; l < 64; l++) for (int q = 0; q < 3; q++) if (hl[l][q] != hl[0][q]) { set_err("wavesim: seed hint not wave-uniform"); return false; }
             for (int q = 0; q < 3; q++) hints[b % 3][q] = hl[0][q];
 #else
-            WAVE_RUN(kb_quant<0, 0>(T, ts.pb10, W, dSD, b, 0, lane_, LQ, QT, -1, nullptr, nullptr, hints[b % 3]));
+            WAVE_RUN(kb_quant<0, 0, 1>(T, ts.pb10, W, dSD, b, 0, lane_, LQ, QT, -1, nullptr, nullptr, hints[b % 3]));
 #endif
         }
     }
     for (;;) {
         W.nflagged[0] = 0; W.nflagged[1] = 0;
         for (int b = 0; b < nfs; b++) kb_validate_fast(T, W, dSD, b);
-        for (int i = 0; i < W.nflagged[1]; i++) WAVE_RUN(kb_validate(T, ts.pb10, W, dSD, W.slow_list[i], lane_, LQ, QT));
+        for (int i = 0; i < W.nflagged[1]; i++) WAVE_RUN(kb_validate<1>(T, ts.pb10, W, dSD, W.slow_list[i], lane_, LQ, QT));
         const int nf = W.nflagged[0];
         if (nf == 0) break;
         repaired += nf; iters++;

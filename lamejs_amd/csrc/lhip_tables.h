@@ -17,6 +17,7 @@ struct TableSet {
     int base_frame_bytes = 0;
     bool bad_option = false;  // build_tables refused an option of the blob -- input gains, frame protection, header flags, the Info tag, ReplayGain (lhip_create: -3)
     InfoTagCfg tag;           // { infoTag } (lhip_infotag.h): host-side only, no kernel sees it
+    bool skip_tail = false;   // the lowpass zeroes the polyphase bands 28..31 (lines 504..575): long blocks end below line 512, launch the batch kernels that skip the dead round of pairs
     int gain_on = 0;          // { replayGain } (lhip_gain.h): the streams of this blob analyse the samples they consume; host-side only
     ~TableSet() { rt::dfree(d_blob); rt::dfree(d_extra); rt::dfree(d_qtabs); }
 };
@@ -247,6 +248,7 @@ static bool derive_index_tables(TableSet& ts, void* stream) {
     extra.resize(amp_at + 64);
     {
         const float* h_af = (const float*)host_arr("amp_filter");
+        ts.skip_tail = (double)h_af[28] < 1e-12 && (double)h_af[29] < 1e-12 && (double)h_af[30] < 1e-12 && (double)h_af[31] < 1e-12;      // (k_fb.h: such a band is zero-filled)
         const int32_t* h_order = (const int32_t*)host_arr("mdct_order");
         double amp[32];
         for (int i = 0; i < 32; i++) amp[i] = 1.0;
