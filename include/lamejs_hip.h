@@ -279,6 +279,9 @@ void lhip_last_batch_stats(int64_t* frames, int64_t* repaired_frames, int64_t* r
 #define LHIP_PATH_INGEST (1u << 14)
 /* (and GAIN 0x8000: the batch held { replayGain } streams: the kernels g_gain_stage and g_gain ran behind it; never set for a stream without the option) */
 #define LHIP_PATH_GAIN (1u << 15)
+/* (and QUANT_FAST 0x10000: the batch's streams were built with { quality: 7 } and its speculative quantization pass was the bin-search-only kernel g_quant_fast
+ *  instead of QUANT_PAIR / QUANT_PERSISTENT; never set for reservoir streams, one-frame calls or with LAMEJS_HIP_NO_FAST_QUANT=1 in the environment) */
+#define LHIP_PATH_QUANT_FAST (1u << 16)
 int lhip_debug_last_paths(uint32_t* mask);
 
 /* Info tag (extension; see above).  What a stream built with { infoTag } has put out so far, and the finished tag frame. */
@@ -316,6 +319,16 @@ int lhip_debug_info_toc(const int64_t* frames, size_t ncalls, int kbps, uint8_t*
  * *windows = complete windows analysed and *samples = samples analysed; 1 with *tenth_db = 0 when no window is complete yet (the reference asserts there);
  * -4 with a message for a stream without the option or one that was moved with lhip_seek / lhip_state_set. */
 int lhip_replay_gain(lhip_stream* s, int32_t* tenth_db, int64_t* windows, int64_t* samples);
+
+/* Quality (extension): a table blob built with { quality: 7 } (tables.js; 8 is resolved to 7) carries the switches of the reference core's fast mode, LAME's
+ * -f (Lame.js:577-588): noise_shaping, noise_shaping_amp, noise_shaping_stop and use_best_huffman 0, subblock_gain -1.  The psychoacoustic model still
+ * decides block switching and mid/side; the quantization of a granule is the bin search for its step size alone (Quantize.js:886-888).  There is no new
+ * entry and no changed record: lhip_create derives one host flag per table set from noise_shaping == 0 && use_best_huffman == 0, and a batch of such
+ * streams without the bit reservoir runs its speculative quantization pass in the kernel g_quant_fast (LHIP_PATH_QUANT_FAST) -- one wave per channel, the bin
+ * search and nothing else; validation, repair and bit packing behind it are the kernels every stream uses.  One-frame calls, reservoir streams and the repair
+ * pass keep the general program, which reads the same switches.  LAMEJS_HIP_NO_FAST_QUANT=1 in the environment (read once per process) sends such batches
+ * through the general quantization kernels as well: the same bytes.  State blobs, lhip_state_bytes, lhip_seek and every other option work as at quality 3;
+ * with { infoTag } the tag reports quality 53 and no noise shaping.  Other quality levels are not in the envelope (tables.js refuses them). */
 /* Test hooks.  lhip_debug_gain_histogram: the stream's 12000 histogram counts (synchronises; same refusals).  lhip_debug_gain_windows: THE KERNELS g_gain_stage and
  * g_gain (in the simulation libraries: their bodies) over n samples per channel (l; r for two channels) as one call of a fresh stream at output rate fs: bins and
  * energies receive floor(n / window) entries, each window's histogram bin and its lsum + rsum.  Returns that number of windows, or < 0. */

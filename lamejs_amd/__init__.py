@@ -22,7 +22,7 @@ _PKG = Path(__file__).resolve().parent
 _LIB_PATH = _PKG / "lib" / "liblamejs_hip.so"
 _TABLE_DIR = _PKG / "tables"
 
-__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED", "PATH_NAMES", "PATH_NAMES_ALL", "PATH_BITS", "PATH_BITS_ALL", "last_batch_paths", "StreamInfo",
+__all__ = ["Mp3Encoder", "load_library", "tables_blob", "LhipError", "encode_streams", "PCM_S16", "PCM_F32", "PCM_INTERLEAVED", "PATH_NAMES", "PATH_NAMES_ALL", "PATH_BITS", "PATH_BITS_ALL", "PATH_BITS_QUALITY", "last_batch_paths", "StreamInfo",
            "PCM_U8", "PCM_S24", "PCM_S32", "PCM_F32N", "PCM_F64N", "PCM_F64", "PCM_BYTES"]
 
 # launch paths of a batch (include/lamejs_hip.h: LHIP_PATH_*), in bit order
@@ -35,6 +35,9 @@ PATH_NAMES_ALL = PATH_BITS[:14]      # (the names up to OUT_CRC, kept for caller
 # ... and GAIN: the batch held ``replay_gain`` streams and the kernels g_gain_stage / g_gain ran behind it.  (A tuple of its own: PATH_BITS is held at its
 # fifteen names by the suite, as PATH_NAMES is at thirteen.)
 PATH_BITS_ALL = PATH_BITS + ("GAIN",)
+# ... and QUANT_FAST: the batch's quantization was the bin-search-only kernel g_quant_fast of ``quality=7`` streams.  (Again a tuple of its own: the suite holds
+# PATH_BITS_ALL at its sixteen names.)  This is the tuple ``last_batch_paths`` decodes with.
+PATH_BITS_QUALITY = PATH_BITS_ALL + ("QUANT_FAST",)
 
 
 def last_batch_paths(lib=None) -> frozenset:
@@ -44,9 +47,9 @@ def last_batch_paths(lib=None) -> frozenset:
     rc = lib.lhip_debug_last_paths(ctypes.byref(m))
     if rc != 0:
         raise LhipError(f"lhip_debug_last_paths failed ({rc}): {lib.lhip_last_error().decode()}")
-    if m.value >> len(PATH_BITS_ALL):
+    if m.value >> len(PATH_BITS_QUALITY):
         raise LhipError(f"lhip_debug_last_paths: unknown bits in {m.value:#x}")
-    return frozenset(n for i, n in enumerate(PATH_BITS_ALL) if m.value >> i & 1)
+    return frozenset(n for i, n in enumerate(PATH_BITS_QUALITY) if m.value >> i & 1)
 
 
 # sample formats of the *_pcm entries (include/lamejs_hip.h: LHIP_PCM_*): a sample type, optionally or-ed with PCM_INTERLEAVED
@@ -181,7 +184,7 @@ def _gain_text(g) -> str:
 
 def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, reservoir: bool = False, fractional_resample: bool = False,
                 downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False, copyright: bool = False, original: bool = True,
-                private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False) -> bytes:
+                private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False, quality: int = 3) -> bytes:
     """The LHTB table blob for a configuration.
 
     Built by the host-side JavaScript ``lamejs_amd/js/tables.js`` (so every transcendental comes
@@ -199,7 +202,13 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     tables.js: the tag's constants as named entries that exist only with the option); without it the blob is the bytes it always was.
     ``replay_gain``: the stream analyses the samples it encodes for its ReplayGain track gain (``{ replayGain }`` of tables.js: one named entry that
     exists only with the option); without it the blob is the bytes it always was.
+    ``quality``: 3 (the reference wrapper's setting) or 7, LAME's ``-f`` (``{ quality }`` of tables.js: the psychoacoustic model still decides block
+    switching and mid/side, the quantization is the bin search alone); 8 is encoded as 7, as the reference's core does.  At 3 the blob is the bytes
+    it always was.
     """
+    if isinstance(quality, bool) or quality not in (3, 7, 8):
+        raise ValueError("quality must be 3, 7 or 8 (8 is encoded as 7)")
+    quality = 7 if quality == 8 else int(quality)
     for name, v in (("protect", protect), ("copyright", copyright), ("original", original), ("private_bit", private_bit), ("info_tag", info_tag), ("replay_gain", replay_gain)):
         if v not in (True, False, 0, 1):
             raise ValueError(f"{name} must be True or False")
@@ -215,6 +224,7 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     mix += (["protect"] if protect else []) + (["copyright"] if copyright else []) + ([] if original else ["original=0"]) + (["privateBit"] if private_bit else []) + ([f"emphasis={int(emphasis)}"] if emphasis else [])
     mix += ["infoTag"] if info_tag else []
     mix += ["replayGain"] if replay_gain else []
+    mix += [f"quality={quality}"] if quality != 3 else []
     f = _TABLE_DIR / f"t_{channels}_{samplerate}_{kbps}{'_joint' if joint else ''}{'_resv' if reservoir else ''}{'_frac' if frac else ''}{''.join('_' + m.replace('=', '') for m in mix)}.bin"
     if not f.exists() or not blob_is_current(f.read_bytes()):      # a cached blob made by another version of its generator is stale
         _TABLE_DIR.mkdir(exist_ok=True)
@@ -269,7 +279,7 @@ class Mp3Encoder:
 
     def __init__(self, channels: int = 1, samplerate: int = 44100, kbps: int = 128, device: int = -1, lib=None, joint: bool = False, reservoir: bool = False,
                  fractional_resample: bool = False, downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False,
-                 copyright: bool = False, original: bool = True, private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False):
+                 copyright: bool = False, original: bool = True, private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False, quality: int = 3):
         """``joint`` (extension, not in the reference's wrapper): encode two channels in the reference's joint-stereo mode --
         per frame mid/side or left/right, as its encoder core decides when asked for MPEGMode.JOINT_STEREO.
         ``reservoir`` (extension): encode with the bit reservoir in use (the reference's wrapper disables it, index.js:108); the frames
@@ -289,12 +299,15 @@ class Mp3Encoder:
         (which is byte for byte the stream without the option), ``stream_info()`` reports the totals, and after ``flush()``
         ``info_tag_frame()`` returns the finished frame to be written over the placeholder at offset 0 (include/lamejs_hip.h, "Info tag").
         ``replay_gain`` (extension): the samples the encoder consumes (behind gains, downmix and resampler) are analysed on the device as the reference
-        core's ReplayGain analysis does; ``replay_gain()`` reports the track gain, and with ``info_tag`` the tag's radio field carries it."""
+        core's ReplayGain analysis does; ``replay_gain()`` reports the track gain, and with ``info_tag`` the tag's radio field carries it.
+        ``quality`` (extension): 3, the reference wrapper's setting, or 7 -- LAME's ``-f``, the reference core's fast mode: block switching and mid/side as
+        always, quantization by the bin search alone (a batch of such streams is quantized by the kernel g_quant_fast).  8 is encoded as 7; any other
+        value raises ``ValueError``."""
         self._lib = lib or load_library()
         self.channels, self.samplerate, self.kbps = int(channels), int(samplerate), int(kbps)
         self._resv = bool(reservoir)
         blob = tables_blob(self.channels, self.samplerate, self.kbps, joint, reservoir, fractional_resample, downmix, scale, scale_left, scale_right,
-                           protect, copyright, original, private_bit, emphasis, info_tag, replay_gain)
+                           protect, copyright, original, private_bit, emphasis, info_tag, replay_gain, quality)
         cfg = _Config(self.channels, self.samplerate, self.kbps, device)
         h = ctypes.c_void_p()
         buf = ctypes.create_string_buffer(blob, len(blob))

@@ -16,6 +16,7 @@
 #if !defined(LHIP_HOSTSIM) || defined(LHIP_WAVESIM)
 #include "k_quant_tail.h"      // how a launch of the persistent quantization kernel ends (the one-lane simulation has no workgroups: it runs kb_quant)
 #endif
+#include "k_quant_fast.h"      // the speculative pass of a fast table set (quality 7): the bin search alone
 #include "k_bits.h"
 #include "k_crc.h"
 #include "k_ingest.h"

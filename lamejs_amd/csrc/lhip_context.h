@@ -61,6 +61,7 @@ struct Context {
     std::map<std::string, std::shared_ptr<TableSet>> tables;
     WorkSet ws;
     int num_cus = 256;
+    int qfast_wg_per_cu[4] = {0, 0, 0, 0};    // resident workgroups per CU of g_quant_fast<PAIR, SKIP> (index 2 PAIR + SKIP; occupancy query at the first launch): its persistent grid is sized by it
     int fixup_wg_per_cu = 0;    // resident g_fixup workgroups per CU (occupancy query at the first cooperative launch)
     // large host-buffer calls (the drop-in's encodeBuffer with a long Int16Array): chunks of the call are copied in on this stream
     // while the chunk before is being encoded and the one before that is copied out (encode_host_chunked)

@@ -149,6 +149,38 @@ template <int RESV, int SKIP> __global__ __launch_bounds__(128, LHIP_QOCC) void 
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     kb_quant<1, RESV, SKIP>(A->T, A->pb, A->W, A->SD, blockIdx.x, A->chain, threadIdx.x & 63, L[wv], Q, wv, mbox);
 }
+// Fast table sets (quality 7): the speculative pass as the bin search alone (k_quant_fast.h), persistent like g_quant.  PAIR == 1 (two channels): the waves
+// 2p, 2p + 1 of a workgroup are a pair -- wave 2p draws the pair's frame slots, each wave quantizes one channel; pairs never wait for each other.  PAIR == 0
+// (one channel): every wave draws its own frames.  The grid is what the device holds of THIS kernel (run_pipeline: occupancy query), not 2 x CUs.
+enum { QF_WAVES = 8 };
+template <int PAIR, int SKIP> __global__ __launch_bounds__(64 * QF_WAVES, LHIP_QOCC) void g_quant_fast(QArgs a_unused) {
+    __shared__ QuantTabs Q;
+    __shared__ QuantLds L[QF_WAVES];
+    __shared__ FastPair FP[QF_WAVES / 2];
+    static_assert(QF_WAVES * sizeof(QuantLds) + sizeof(QuantTabs) + sizeof(FP) <= 80 * 1024, "g_quant_fast: LDS budget for 2 workgroups per CU exceeded");
+    static_assert(sizeof(FP) / sizeof(int) <= 64 * QF_WAVES, "the pair records are zeroed by one store per thread");
+    const QArgs* A = (const QArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    q_copy_tabs(A->T, Q, threadIdx.x, 64 * QF_WAVES);
+    if (threadIdx.x < sizeof(FP) / sizeof(int)) ((int*)FP)[threadIdx.x] = 0;
+    __syncthreads();
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    int hint[3] = {-1, -1, -1};                       // stream and bin-search results of this wave's previous frame (kb_quant_fast: speculation seed)
+    for (int round = 1;; round++) {
+        int fslot;
+        if constexpr (PAIR != 0) {
+            FastPair& fp = FP[wv >> 1];
+            if ((wv & 1) == 0) { fslot = next_frame_slot(A->W.work_ctr + A->ctr); fast_pair_publish_slot(fp, round, fslot, lane); }
+            else fslot = fast_pair_await_slot(fp, round, lane);
+            if (fslot >= A->nfs) break;
+            kb_quant_fast<1, SKIP>(A->T, A->pb, A->W, A->SD, fslot, lane, L[wv], Q, hint, wv & 1, &fp, round);
+        } else {
+            fslot = next_frame_slot(A->W.work_ctr + A->ctr);
+            if (fslot >= A->nfs) break;
+            kb_quant_fast<0, SKIP>(A->T, A->pb, A->W, A->SD, fslot, lane, L[wv], Q, hint);
+        }
+        hint[0] = __builtin_amdgcn_readfirstlane(hint[0]); hint[1] = __builtin_amdgcn_readfirstlane(hint[1]); hint[2] = __builtin_amdgcn_readfirstlane(hint[2]);
+    }
+}
 __global__ __launch_bounds__(256) void g_validate_fast(Tables T, Workspace W, const StreamDesc* SD, int nfs) {
     __shared__ ValidateShare S;
     const int t = blockIdx.x * 256 + threadIdx.x, fslot = t >> 2;        // four lanes per frame slot (kb_validate_fast_quad)

@@ -100,7 +100,24 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     static const int pair_max = []() { const char* e = getenv("LAMEJS_HIP_PAIR_MAX_FRAMES"); return e ? atoi(e) : -1; }();
     const bool pair = (C == 2 && nfs <= (pair_max >= 0 ? pair_max : 6 * ctx->num_cus));
 #endif
-    P.paths |= pair ? LHIP_PATH_QUANT_PAIR : LHIP_PATH_QUANT_PERSISTENT;
+    const bool fastq = ts.fast && fast_quant_allowed();
+    P.paths |= fastq ? LHIP_PATH_QUANT_FAST : pair ? LHIP_PATH_QUANT_PAIR : LHIP_PATH_QUANT_PERSISTENT;
+    if (fastq) {
+        // a fast table set (quality 7): the bin-search-only kernel, one wave per channel at every batch size; as many workgroups as the device holds of it
+        QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;
+        const void* const fns[4] = {(const void*)g_quant_fast<0, 0>, (const void*)g_quant_fast<0, 1>, (const void*)g_quant_fast<1, 0>, (const void*)g_quant_fast<1, 1>};
+        int& wg_per_cu = ctx->qfast_wg_per_cu[(C == 2 ? 2 : 0) + (ts.skip_tail ? 1 : 0)];
+        if (wg_per_cu == 0) {
+            int nb = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fns[(C == 2 ? 2 : 0) + (ts.skip_tail ? 1 : 0)], 64 * QF_WAVES, 0) != hipSuccess || nb < 1) nb = 1;
+            wg_per_cu = nb;
+        }
+        const int per_wg = C == 2 ? QF_WAVES / 2 : QF_WAVES;      // frames in flight per workgroup
+        int fq = (nfs + per_wg - 1) / per_wg;
+        if (fq > ctx->num_cus * wg_per_cu) fq = ctx->num_cus * wg_per_cu;
+        if (C == 2) { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant_fast<1, 1>), fq, 64 * QF_WAVES, st, qa); else LAUNCHB(KT_QUANT, (g_quant_fast<1, 0>), fq, 64 * QF_WAVES, st, qa); }
+        else { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant_fast<0, 1>), fq, 64 * QF_WAVES, st, qa); else LAUNCHB(KT_QUANT, (g_quant_fast<0, 0>), fq, 64 * QF_WAVES, st, qa); }
+    } else
     { QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;
       // (which form is a matter of speed only: the skip itself is decided per granule-channel from its spectrum)
       if (pair) { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant_pair<0, 1>), nfs, 128, st, qa); else LAUNCHB(KT_QUANT, (g_quant_pair<0, 0>), nfs, 128, st, qa); }

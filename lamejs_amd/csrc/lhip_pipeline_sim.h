@@ -29,7 +29,9 @@ static inline bool g_kt_on_() { return false; }
 static bool collect_kernel_times(void*) { return true; }
 static bool collect_repair_stats(Context*, BatchPlan&, bool, const int32_t*) { return true; }      // (run_pipeline counted them itself)
 // P.paths: the simulations record what they simulate -- the scalar one has no two-waves-per-frame program and no count helpers, the wave
-// simulation always runs the count helpers, and neither has g_fixup's two launch forms (the repair is the host loop below): no FIXUP bit
+// simulation always runs the count helpers, and neither has g_fixup's two launch forms (the repair is the host loop below): no FIXUP bit.
+// A fast table set's speculative pass is kb_quant_fast (QUANT_FAST): frame by frame in the scalar simulation, g_quant_fast's workgroup of
+// pairs (two channels) or of single waves (one channel) in the wave simulation.
 static bool run_pipeline(Context* ctx, BatchPlan& P) {
     const TableSet& ts = *P.ts; const Tables& T = ts.T; Workspace& W = P.W; const std::vector<StreamDesc>& sd = P.sd;
     const StreamDesc* dSD = P.dSD; const StreamIO* dIO = P.dIO;
@@ -122,10 +124,43 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     static thread_local QuantLds LQ2[2]; static thread_local int mbox[4];
     static const int pair_max = []() { const char* e = getenv("LAMEJS_HIP_PAIR_MAX_FRAMES"); return e ? atoi(e) : 12; }();
     const bool pair = (C == 2 && nfs <= pair_max);
-    P.paths |= pair ? LHIP_PATH_QUANT_PAIR : LHIP_PATH_QUANT_PERSISTENT;
-#else
-    P.paths |= LHIP_PATH_QUANT_PERSISTENT;
 #endif
+    const bool fastq = ts.fast && fast_quant_allowed();
+#ifdef LHIP_WAVESIM
+    P.paths |= fastq ? LHIP_PATH_QUANT_FAST : pair ? LHIP_PATH_QUANT_PAIR : LHIP_PATH_QUANT_PERSISTENT;
+#else
+    P.paths |= fastq ? LHIP_PATH_QUANT_FAST : LHIP_PATH_QUANT_PERSISTENT;
+#endif
+    if (fastq) {
+#if defined(LHIP_WAVESIM)
+        // g_quant_fast as a real 8-wave workgroup: the frame slots drawn from a shared counter, by every wave (one channel) or by wave 0 of every pair
+        static thread_local QuantLds LF[8]; static thread_local FastPair FP[4];
+        int ctr = 0;
+        memset(FP, 0, sizeof FP);
+        wsim::run_block(8, [&](int wave_, int lane_) {
+            int hint[3] = {-1, -1, -1};
+            for (int round = 1;; round++) {
+                int f = 0;
+                if (C == 2) {
+                    FastPair& fp = FP[wave_ >> 1];
+                    if ((wave_ & 1) == 0) { if (lane_ == 0) f = ctr++; f = wave_bcast(f, 0); fast_pair_publish_slot(fp, round, f, lane_); }
+                    else f = fast_pair_await_slot(fp, round, lane_);
+                    if (f >= nfs) break;
+                    kb_quant_fast<1, 1>(T, ts.pb10, W, dSD, f, lane_, LF[wave_], QT, hint, wave_ & 1, &fp, round);
+                } else {
+                    if (lane_ == 0) f = ctr++;
+                    f = wave_bcast(f, 0);
+                    if (f >= nfs) break;
+                    kb_quant_fast<0, 1>(T, ts.pb10, W, dSD, f, lane_, LF[wave_], QT, hint);
+                }
+            }
+        });
+#else
+        // three "persistent waves" striding over the frame slots, each with its own seed hint (as the general pass below)
+        int hints[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};
+        for (int b = 0; b < nfs; b++) WAVE_RUN(kb_quant_fast<0, 1>(T, ts.pb10, W, dSD, b, lane_, LQ, QT, hints[b % 3]));
+#endif
+    } else
 #if defined(LHIP_WAVESIM)
     if (!pair) {   // the persistent kernel as a real 8-wave workgroup: frames drawn from a shared counter (kb_quant_th, what g_quant runs for one- and
                     // two-channel streams alike), then -- two channels -- the waves help each other (k_quant_tail.h)

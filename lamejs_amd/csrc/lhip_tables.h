@@ -19,8 +19,13 @@ struct TableSet {
     InfoTagCfg tag;           // { infoTag } (lhip_infotag.h): host-side only, no kernel sees it
     bool skip_tail = false;   // the lowpass zeroes the polyphase bands 28..31 (lines 504..575): long blocks end below line 512, launch the batch kernels that skip the dead round of pairs
     int gain_on = 0;          // { replayGain } (lhip_gain.h): the streams of this blob analyse the samples they consume; host-side only
+    bool fast = false;        // { quality: 7 }: no noise shaping and no Huffman region search -- a batch's speculative quantization pass is g_quant_fast (k_quant_fast.h)
     ~TableSet() { rt::dfree(d_blob); rt::dfree(d_extra); rt::dfree(d_qtabs); }
 };
+
+// LAMEJS_HIP_NO_FAST_QUANT=1 (read once per process): fast table sets go through the general quantization kernels, which read the same switches (the A/B
+// of g_quant_fast, and a second yardstick for it)
+static bool fast_quant_allowed() { static const bool off = []() { const char* e = getenv("LAMEJS_HIP_NO_FAST_QUANT"); return e && e[0] == '1'; }(); return !off; }
 
 static const lhtb_entry* find_entry(const uint8_t* b, const char* name) {
     uint32_t n; memcpy(&n, b + 8, 4);
@@ -169,8 +174,9 @@ static bool check_envelope(TableSet& ts, const lhip_config& cfg) {
     }
     if ((T.version != 1 && T.version != 0) || T.mode_gr != (T.version == 1 ? 2 : 1) || T.quant_comp != 9 || T.quant_comp_short != 9 || T.sfb21_extra ||
         T.substep_shaping != 0 || T.noise_shaping_amp > 2 || T.use_best_huffman > 1 || T.athaa_loudapprox != 2 || T.full_outer_loop != 0) {
-        set_err("configuration outside the supported envelope (MPEG-1/2/2.5 CBR, quality-3 switches)"); return false;
+        set_err("configuration outside the supported envelope (MPEG-1/2/2.5 CBR, the switches of quality 3 or 7)"); return false;
     }
+    ts.fast = T.noise_shaping == 0 && T.use_best_huffman == 0;
     // frame protection and header flags (extension { protect, copyright, original, privateBit, emphasis }): the side information of a protected stream is
     // two bytes longer (Lame.js:1109-1110) -- every budget reads sideinfo_len, so it must be the mode's value plus exactly what the flag says
     {

@@ -43,6 +43,10 @@
  * depend on how the stream is cut into calls; nothing is read back until replayGain() or infoTagFrame() asks.  With { infoTag } the tag frame's radio
  * ReplayGain field carries the value (peak amplitude and the audiophile field stay zero).  With every option above, encodeBatch() of such encoders beside
  * others and { pendingFrames } included; refused at construction on a { fractionalResample } stream that resamples; not after seek() / setState().
+ * Extension { quality: 7 }: LAME's -f, the fast mode of the reference's encoder core (its wrapper always asks for quality 3): block switching and mid/side
+ * decisions as always, the quantization of a granule is the bin search for its step size alone -- no noise shaping, no Huffman region search -- so the
+ * bytes are those of the reference core with gfp.quality = 7, and a batch is quantized by a kernel of its own (g_quant_fast).  8 is encoded as 7, as the
+ * core does; 3 is the default; any other value is a RangeError.  With every option above, encodeBatch() of encoders of both qualities included.
  * Extension { fractionalResample: true }: the 49 (channels, sample rate, kbps) triples the reference resamples by a non-integer ratio -- refused
  * by default, because the reference feeds itself NaN samples there once a call is long enough -- are accepted as call-sequence streams: every
  * encodeBuffer() gives the reference's bytes for the same sequence of call lengths; a call longer than the reference consumes whole throws
@@ -75,7 +79,8 @@ const blobCache = new Map();
 function tablesBlob(channels, samplerate, kbps, opts) {
     const key = [channels, samplerate, kbps, opts && opts.jointStereo ? 1 : 0, opts && opts.reservoir ? 1 : 0, opts && opts.fractionalResample ? 1 : 0,
         opts && opts.downmix ? 1 : 0, opts ? String(opts.scale) : '', opts ? String(opts.scaleLeft) : '', opts ? String(opts.scaleRight) : '',
-        opts ? ['protect', 'copyright', 'original', 'privateBit', 'emphasis'].map((k) => String(opts[k])).join(',') : '', opts && opts.infoTag ? 1 : 0, opts && opts.replayGain ? 1 : 0].join('|');     /* (pendingFrames is host-side only) */
+        opts ? ['protect', 'copyright', 'original', 'privateBit', 'emphasis'].map((k) => String(opts[k])).join(',') : '', opts && opts.infoTag ? 1 : 0, opts && opts.replayGain ? 1 : 0,
+        opts ? typeof opts.quality + String(opts.quality) : ''].join('|');     /* (quality with its type: '7' is refused, not served 7's blob; pendingFrames is host-side only) */
     let blob = blobCache.get(key);
     if (!blob) { blob = tables.buildBlob(channels, samplerate, kbps, opts).blob; blobCache.set(key, blob); }
     return blob;

@@ -11,7 +11,7 @@
  *   index.js:100-111        fixed Mp3Encoder configuration
  *   Lame.js:747-1371        lame_init_params (CBR, vbr_off branch only)
  *   Lame.js:470-558         polyphase low-pass amplitudes (amp_filter)
- *   Lame.js:560-690         quality map (quality 3)
+ *   Lame.js:560-690         quality map (quality 3; 7 with { quality: 7 })
  *   Presets.js:226-358      ABR preset row applied for CBR
  *   QuantizePVT.js:247-414  ATH per sfb, pow43/adj43/ipow20/pow20, long/shortfact
  *   Takehiro.js:1141-1172   bv_scf region split table
@@ -302,6 +302,24 @@ function resolveParams(channels, samplerate, kbps, opts) {
     p.full_outer_loop = 0;
     p.substep_shaping = 0;
     p.sfb21_extra = 0;
+    /* extension { quality }: LAME's -f, quality 7 of the reference's encoder core (its wrapper always asks for 3) -- the psychoacoustic model still
+     * decides block switching and mid/side, the quantization is the bin search alone: no noise shaping (even where the preset row asked for
+     * type 2), no amplification, no Huffman region search; subblock_gain stays at lame_init_params' -1 (Lame.js:145, 577-588).  8 is resolved
+     * to 7 as lame_init_qval does (Lame.js:574-576).  The other levels differ in more than switches and are not in the envelope. */
+    p.quality = 3;
+    if (opts && opts.quality !== undefined && opts.quality !== null) {
+        if (opts.quality !== 3 && opts.quality !== 7 && opts.quality !== 8) throw new RangeError('lamejs_amd: { quality } must be 3, 7 or 8 (8 is encoded as 7)');
+        p.quality = opts.quality == 8 ? 7 : opts.quality;
+    }
+    if (p.quality == 7) {
+        p.psymodel = 1;
+        p.noise_shaping = 0;
+        p.noise_shaping_amp = 0;
+        p.noise_shaping_stop = 0;
+        p.subblock_gain = -1;
+        p.use_best_huffman = 0;
+        p.full_outer_loop = 0;
+    }
 
     p.ATH_useAdjust = 3;
     p.ATH_aaSensitivityP = Math.pow(10.0, 0.0 / -10.0);
@@ -686,13 +704,13 @@ function buildBlob(channels, samplerate, kbps, opts) {
     }
     /* { infoTag }: what the tag frame reports besides the stream's totals, resolved here as putLameVBR does (VBRTag.js:576-732) -- named entries that
      * exist only with the option (a blob without it is the bytes it always was).  quality: 100 - 10 VBR_q - quality with lame_init's VBR_q = 4 and
-     * the wrapper's quality 3; method 1 (CBR); lowpass in units of 100 Hz; flags: ATHtype + (exp_nspsytune << 4), i.e. the nspsytune and the
+     * the stream's quality (3, or 7 with { quality }); method 1 (CBR); lowpass in units of 100 Hz; flags: ATHtype + (exp_nspsytune << 4), i.e. the nspsytune and the
      * safe-joint bit; misc: noise_shaping + (stereoMode << 2) + (nonOptimal << 5) + (sourceFreq << 6) by VBRTag.js:686-732 -- a downmix is MONO,
      * unequal channel gains, a disabled reservoir below 320 kbps and an input rate of at most 32 kHz are "non-optimal"; preset: the bitrate that
      * selected the ABR preset row (Lame.js:1216-1218, Presets.js:415); delay: Encoder.ENCDELAY */
     let tagVersion = null;
     if (p.info_tag) {
-        const VBR_q = 4, quality = 3;
+        const VBR_q = 4, quality = p.quality;
         const stereoMode = p.mode == MODE_MONO ? 0 : p.mode == MODE_STEREO ? 1 : 3;
         const sourceFreq = samplerate <= 32000 ? 0 : samplerate == 48000 ? 2 : samplerate > 48000 ? 3 : 1;
         const nonOptimal = (p.scale_left < p.scale_right || p.scale_left > p.scale_right || (p.disable_reservoir && p.brate < 320) || p.ATHtype == 0 || samplerate <= 32000) ? 1 : 0;
@@ -765,13 +783,13 @@ module.exports = { buildBlob, resolveParams, buildTables, packBlob, sourceHash, 
 
 if (require.main === module) {
     /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] [fracresample] [downmix] [scale=G] [scaleLeft=G] [scaleRight=G]
-     *      [protect] [copyright] [original=0|1] [privateBit] [emphasis=E] [infoTag] [replayGain] */
+     *      [protect] [copyright] [original=0|1] [privateBit] [emphasis=E] [infoTag] [replayGain] [quality=3|7|8] */
     const [ch, sr, kb, out] = process.argv.slice(2), flags = process.argv.slice(6);
     const opts = { jointStereo: flags.includes('joint'), reservoir: flags.includes('reservoir'), fractionalResample: flags.includes('fracresample') };
     if (flags.includes('downmix')) opts.downmix = true;
     for (const f of flags) { const m = /^(scale|scaleLeft|scaleRight)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
     for (const k of ['protect', 'copyright', 'privateBit', 'infoTag', 'replayGain']) if (flags.includes(k)) opts[k] = true;
-    for (const f of flags) { const m = /^(original|emphasis)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
+    for (const f of flags) { const m = /^(original|emphasis|quality)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
     const r = buildBlob(+ch, +sr, +kb, opts);
     require('fs').writeFileSync(out, r.blob);
     console.log('wrote', out, r.blob.length, 'bytes');
