@@ -327,7 +327,9 @@ int lhip_replay_gain(lhip_stream* s, int32_t* tenth_db, int64_t* windows, int64_
  * streams without the bit reservoir runs its speculative quantization pass in the kernel g_quant_fast (LHIP_PATH_QUANT_FAST) -- one wave per channel, the bin
  * search and nothing else; validation, repair and bit packing behind it are the kernels every stream uses.  One-frame calls, reservoir streams and the repair
  * pass keep the general program, which reads the same switches.  LAMEJS_HIP_NO_FAST_QUANT=1 in the environment (read once per process) sends such batches
- * through the general quantization kernels as well: the same bytes.  State blobs, lhip_state_bytes, lhip_seek and every other option work as at quality 3;
+ * through the general quantization kernels as well: the same bytes.  LAMEJS_HIP_QUANT_GRID_MAX=<n>, n >= 1 (a test hook, read once per process) launches the
+ * persistent speculative quantization kernels, g_quant_fast and g_quant, with at most n workgroups -- with 1, every wave or pair of waves of the one workgroup
+ * takes frame after frame -- and touches no other kernel's grid; unset or < 1 it changes nothing.  lhip_debug_read(11) reports the launch.  State blobs, lhip_state_bytes, lhip_seek and every other option work as at quality 3;
  * with { infoTag } the tag reports quality 53 and no noise shaping.  Other quality levels are not in the envelope (tables.js refuses them). */
 /* Test hooks.  lhip_debug_gain_histogram: the stream's 12000 histogram counts (synchronises; same refusals).  lhip_debug_gain_windows: THE KERNELS g_gain_stage and
  * g_gain (in the simulation libraries: their bodies) over n samples per channel (l; r for two channels) as one call of a fresh stream at output rate fs: bins and
@@ -344,6 +346,11 @@ int lhip_debug_ingest(int format, int channels, const void* bytes, size_t nsampl
  * what: 0 xr [granule][ch][576] f32, 1 blocktype [granule][ch] i32, 2 E [granule][psy ch][122] f32 (psy ch = ch, or L R mid side in joint stereo; thresholds
  * handed to the quantizer for that granule), 3 ath_adjust [frame] f64, 4 side records (struct GrSide); simulation libraries only: 10 two i64, the
  * evaluations of the quantization search this process has made without / with the last round of pairs (lines 512..575 all zero / not).
+ * 11 (every library; needs no batch to have run): eight i32, the speculative quantization launch of the calling thread's most recent batch -- [0] workgroups
+ * launched, [1] waves per workgroup, [2] frame slots, [3] the kernel (1 g_quant_fast, 2 g_quant_pair, 3 g_quant), [4] [5] its PAIR and SKIP template arguments
+ * (g_quant_pair: PAIR 1, g_quant: 0), [6] [7] zero; all zero when the batch launched none (one-frame program, bit reservoir).  The wave simulation reports the
+ * one 8-wave workgroup it runs (the pair program: a two-wave workgroup per frame slot), the scalar simulation its three striding waves as one workgroup of 3;
+ * both run the SKIP = 1 bodies and report in [5] the form the device launches for the table set.
  * Returns bytes copied or <0. */
 int64_t lhip_debug_read(int what, void* dst, size_t cap);
 

@@ -678,6 +678,10 @@ int lhip_debug_last_paths(uint32_t* mask) {
 }
 
 int64_t lhip_debug_read(int what, void* dst, size_t cap) {
+    if (what == 11) {                                   // the speculative quantization launch of this thread's last batch (QuantLaunch, lhip_rt.h): eight int32
+        if (!dst) { set_err("lhip_debug_read: null argument"); return LHIP_ERR_INTERNAL; }
+        const size_t n = cap < sizeof g_last_quant ? cap : sizeof g_last_quant; memcpy(dst, &g_last_quant, n); return (int64_t)n;
+    }
 #ifdef LHIP_HOSTSIM
     if (what == 10) {                                   // evaluations so far with the short / the full round count (RoundStats, k_quant.h)
         const int64_t v[2] = {(int64_t)__atomic_load_n(&round_stats().head, __ATOMIC_RELAXED), (int64_t)__atomic_load_n(&round_stats().full, __ATOMIC_RELAXED)};

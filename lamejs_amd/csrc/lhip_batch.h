@@ -126,6 +126,7 @@ struct BatchPlan {
     int ingest = 0, ingest_tiles = 0; size_t ingest_floats = 0; const IngestDesc* dING = nullptr;
     int S = 0, nfs = 0, ngs = 0, nfr = 0, maxF = 0;
     uint32_t paths = 0;                            // LHIP_PATH_*: one bit per launch decision run_pipeline really takes for this batch (host-side record only)
+    QuantLaunch ql;                                // ... and the shape of its speculative quantization launch (lhip_debug_read(11))
     int64_t pcm_plane = 0, in_total = 0, out_total = 0, repaired = 0, iters = 0;
     size_t in_bytes = 0, FR = 1;                   // in_bytes: host input as it travels: every job's samples in its format, jobs 4-byte aligned
     std::vector<StreamDesc> sd; std::vector<StreamIO> io;
@@ -482,7 +483,7 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     advance_streams(jobs, P.ts->T);
     if (P.crc_mode && !crc_log) for (int i = 0; i < P.S; i++) tag_account(*jobs[i].s->tag, jobs[i].F, jobs[i].bytes, P.crc[i], P.ts->T.brate);
     if (!collect_repair_stats(ctx, P, fetch_fx, fx)) return false;
-    g_stat_frames = P.nfr; g_stat_repaired = P.repaired; g_stat_iters = P.iters; g_last_paths = P.paths;
+    g_stat_frames = P.nfr; g_stat_repaired = P.repaired; g_stat_iters = P.iters; g_last_paths = P.paths; g_last_quant = P.ql;
     WorkSet& ws = ctx->ws;
     ws.lastW = P.W; ws.lastC = P.ts->T.channels_out; ws.lastCp = P.ts->T.psy_channels; ws.have_last = true;
     return true;

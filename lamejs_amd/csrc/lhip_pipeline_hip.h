@@ -14,6 +14,13 @@ static bool collect_repair_stats(Context* ctx, BatchPlan& P, bool fetch_fx, cons
     } else if (P.nfr > 0) g_stat_pending = ctx;
     return true;
 }
+// LAMEJS_HIP_QUANT_GRID_MAX=<n>, n >= 1 (read once per process; a test hook): at most n workgroups for the persistent speculative quantization launches,
+// g_quant_fast and g_quant -- with n = 1 every wave (pair) of the one workgroup takes frame after frame at a few frames already.  Unset or < 1: no cap.
+// No other kernel's grid is touched (g_quant_pair is one workgroup per frame, g_fixup's grid decides its launch form, g_resv_stream's is the streams).
+static int quant_grid_cap(int grid) {
+    static const int cap = []() { const char* e = getenv("LAMEJS_HIP_QUANT_GRID_MAX"); return e ? atoi(e) : 0; }();
+    return cap >= 1 && grid > cap ? cap : grid;
+}
 static bool run_pipeline(Context* ctx, BatchPlan& P) {
     const TableSet& ts = *P.ts; const Tables& T = ts.T; Workspace& W = P.W; const std::vector<StreamDesc>& sd = P.sd;
     const StreamDesc* dSD = P.dSD; const StreamIO* dIO = P.dIO;
@@ -91,6 +98,7 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     // persistent quantization kernels: as many workgroups as can be resident (2 per CU), frames dispensed dynamically
     int qgrid = (nfs + QWAVES - 1) / QWAVES;
     if (qgrid > ctx->num_cus * 2) qgrid = ctx->num_cus * 2;
+    qgrid = quant_grid_cap(qgrid);
 #ifdef LHIP_PHASE_PROF
     const bool pair = false;
 #else
@@ -115,10 +123,13 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
         const int per_wg = C == 2 ? QF_WAVES / 2 : QF_WAVES;      // frames in flight per workgroup
         int fq = (nfs + per_wg - 1) / per_wg;
         if (fq > ctx->num_cus * wg_per_cu) fq = ctx->num_cus * wg_per_cu;
+        fq = quant_grid_cap(fq);
+        P.ql.workgroups = fq; P.ql.waves = QF_WAVES; P.ql.nfs = nfs; P.ql.kernel = QL_FAST; P.ql.pair = C == 2; P.ql.skip = ts.skip_tail;
         if (C == 2) { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant_fast<1, 1>), fq, 64 * QF_WAVES, st, qa); else LAUNCHB(KT_QUANT, (g_quant_fast<1, 0>), fq, 64 * QF_WAVES, st, qa); }
         else { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant_fast<0, 1>), fq, 64 * QF_WAVES, st, qa); else LAUNCHB(KT_QUANT, (g_quant_fast<0, 0>), fq, 64 * QF_WAVES, st, qa); }
     } else
     { QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;
+      P.ql.workgroups = pair ? nfs : qgrid; P.ql.waves = pair ? 2 : QWAVES; P.ql.nfs = nfs; P.ql.kernel = pair ? QL_PAIR : QL_PERSISTENT; P.ql.pair = pair; P.ql.skip = ts.skip_tail;
       // (which form is a matter of speed only: the skip itself is decided per granule-channel from its spectrum)
       if (pair) { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant_pair<0, 1>), nfs, 128, st, qa); else LAUNCHB(KT_QUANT, (g_quant_pair<0, 0>), nfs, 128, st, qa); }
       else { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant<0, 1>), qgrid, 64 * QWAVES, st, qa); else LAUNCHB(KT_QUANT, (g_quant<0, 0>), qgrid, 64 * QWAVES, st, qa); } }

@@ -126,6 +126,15 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     const bool pair = (C == 2 && nfs <= pair_max);
 #endif
     const bool fastq = ts.fast && fast_quant_allowed();
+    // the launch record (lhip_debug_read(11)): what is simulated -- one 8-wave workgroup, or the pair program's one workgroup of two waves per frame slot, in the
+    // wave simulation; the three striding "waves" of the scalar one as one workgroup of 3.  Both run the SKIP = 1 bodies, which decide per granule-channel: `skip`
+    // reports the table set's skip_tail, the form the device launches for it.
+#ifdef LHIP_WAVESIM
+    P.ql.workgroups = (!fastq && pair) ? nfs : 1; P.ql.waves = (!fastq && pair) ? 2 : 8; P.ql.kernel = fastq ? QL_FAST : pair ? QL_PAIR : QL_PERSISTENT; P.ql.pair = fastq ? C == 2 : pair;
+#else
+    P.ql.workgroups = 1; P.ql.waves = 3; P.ql.kernel = fastq ? QL_FAST : QL_PERSISTENT; P.ql.pair = fastq && C == 2;
+#endif
+    P.ql.nfs = nfs; P.ql.skip = ts.skip_tail;
 #ifdef LHIP_WAVESIM
     P.paths |= fastq ? LHIP_PATH_QUANT_FAST : pair ? LHIP_PATH_QUANT_PAIR : LHIP_PATH_QUANT_PERSISTENT;
 #else

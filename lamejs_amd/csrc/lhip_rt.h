@@ -18,6 +18,11 @@ struct Context;
 static thread_local Context* g_rej_pending = nullptr;       // the last batch counted rejected Float32 samples on the device (lhip_last_batch_rejected_samples fetches the count)
 static thread_local int64_t g_rejected = 0;
 static thread_local uint32_t g_last_paths = 0;              // launch decisions of the last batch (LHIP_PATH_* of include/lamejs_hip.h; lhip_debug_last_paths)
+// the speculative quantization launch of the last batch (lhip_debug_read(11), a test hook): all zero when the batch launched none (one-frame program, reservoir).
+// kernel: 1 g_quant_fast, 2 g_quant_pair, 3 g_quant; pair / skip: the PAIR and SKIP template arguments (g_quant_pair: pair = 1, g_quant: pair = 0)
+struct QuantLaunch { int32_t workgroups = 0, waves = 0, nfs = 0, kernel = 0, pair = 0, skip = 0, pad_[2] = {0, 0}; };
+enum { QL_FAST = 1, QL_PAIR = 2, QL_PERSISTENT = 3 };
+static thread_local QuantLaunch g_last_quant;
 static thread_local Context* g_stat_pending = nullptr;      // the last batch was enqueued without synchronisation: its repair statistics are still on the device
 static void set_err(const std::string& e) { g_err = e; }
 

@@ -15,6 +15,8 @@ material         tests/tools/fuzz_gpu.material under fixed seeds (attacks, hence
                  two stretches of digital silence of four and five frames (a silent granule-channel makes no evaluation and leaves an all-zero
                  working spectrum; the noise's onset is a short block -- five rounds -- and the long blocks behind it run four), and
                  pcm.CORPORA["sine"] at 320 kbps (no granule-channel may take the short form)
+quality 7        the twins of six cases (Q7_TWINS) with { quality: 7 }: a batch call takes kb_quant_fast / g_quant_fast, whose unit (q_unit_fast) decides the
+                 flag and zeroes the words itself
 the stale words  At 44.1 / 48 kHz the lines 512..575 lie in the last band, beyond big_values, count1 and every band the search evaluates: nothing reads
                  the words 256..287 there, with or without the zeroing.  At 32 kHz band 20 straddles line 512, and the simulations poison those
                  words at the entry of every granule-channel (q_unit, host-only): with the zeroing statement removed from q_unit, 32000/96 stereo
@@ -57,6 +59,18 @@ CASES = [
 ]
 for _i, _c in enumerate(CASES):
     _c.setdefault("seed", SEED + _i)
+# quality 7: the fast unit has code of its own for the skipped round (q_fast_limits' tail0, the zeroing statement of q_unit_fast).  Each case is the twin of
+# a quality-3 one: same configuration, same material, same seed.  `silence`: an inactive unit leaves an all-zero working spectrum in front of a four-round
+# unit of the same wave.
+Q7_TWINS = ("stereo128/fuzz", "stereo128/silence", "stereo320/fuzz", "lsf64/fuzz", "stereo32k96/fuzz", "mono32k48/fuzz")
+CASES += [dict(next(c for c in CASES if c["name"] == _n), name="q7/" + _n, opts={"quality": 7}) for _n in Q7_TWINS]
+# ... and the stream in which the fast unit's zeroing statement decides bytes.  Behind the bin search the fast mode reads the lines 512..549 in one place
+# only, the empty-band scan of q_best_scalefac_store (the count of a tail0 search never reads them, g_bits stops at big_values + count1 <= 512).  All
+# scalefactors are zero there, so whether band 20 is marked empty matters to the preflag test alone: preflag is set when the bands 11..20 are ALL empty, that
+# is when an active long-block granule quantizes to zero from line 66 (1.8 kHz) up.  The fuzz material never does; loud noise cut off at 1.5 kHz does in half
+# of its granules, and with the statement removed from q_unit_fast this case differs from the oracle from its 2-frame call on (both simulations; 32000/48
+# one channel from the 9-frame call on).  32000/80 is the two-channel 32 kHz configuration whose lowpass zeroes the lines 512..575 (96 kbps keeps them).
+CASES.append(dict(name="q7/stereo32k80/lownoise", ch=2, sr=32000, kb=80, opts={"quality": 7}, material="lownoise", seed=7400))
 
 
 def case(name):
@@ -79,6 +93,13 @@ def case_pcm(c, n):
         for a, b in SILENT:
             L[1152 * a:1152 * b] = 0
             R[1152 * a:1152 * b] = 0
+    elif c["material"] == "lownoise":     # white noise without its bins above 1.5 kHz, peak 30000
+        def plane():
+            X = np.fft.rfft(rng.standard_normal(n))
+            X[int(1500.0 * n / c["sr"]):] = 0
+            x = np.fft.irfft(X, n)
+            return np.round(x * (30000 / np.abs(x).max())).astype(np.int16)
+        L, R = plane(), plane()
     else:
         L, R = pcm.CORPORA[c["material"]](n, c["ch"])
         L, R = np.asarray(L, dtype=np.int16), None if R is None else np.asarray(R, dtype=np.int16)

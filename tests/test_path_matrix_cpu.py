@@ -4,7 +4,13 @@ expectations, the side-information reader and the path bookkeeping are proven on
 * the scalar simulation runs the full shapes; it has no two-waves-per-frame program, so LAMEJS_HIP_PAIR_MAX_FRAMES cannot change what it
   runs: its children are the default environment and the one with both switches;
 * the wave simulation runs the shapes capped at 17 frames, in the default environment (pair program up to 12 frame slots) and with
-  LAMEJS_HIP_PAIR_MAX_FRAMES=0 (the persistent workgroup with its tail help at every shape)."""
+  LAMEJS_HIP_PAIR_MAX_FRAMES=0 (the persistent workgroup with its tail help at every shape);
+* both run the list once more with LAMEJS_HIP_NO_FAST_QUANT=1: the quality-7 cases through the general kernel bodies.  LAMEJS_HIP_QUANT_GRID_MAX
+  does not exist in the simulations: the wave simulation's g_quant_fast and g_quant are one workgroup already, and its launch records must say so.
+
+Children's wall time measured here (the worker's own clock): the scalar simulation's 52 cases and 12 506 frames took 18.4 s (default), 17.5 s (both)
+and 18.3 s (nofast) -- 17 s with the 37 quality-3 cases alone; the wave simulation's 46 cases and 1 452 frames took 72 s (default), 85 s (pair0) and 68 s
+(nofast) beside other work on the machine.  The limits, 600 s and 1800 s, are more than twenty times that and only end a child that hangs."""
 import numpy as np
 import pytest
 
@@ -31,8 +37,59 @@ def test_case_list_is_the_one_asked_for():
     for c in cs:
         if not c["resv"]:               # a sequence crosses paths: a one-frame call, a remainder and batches on both sides of eight waves
             assert 1 in c["seq"] and 0 in c["seq"] and min(f for f in c["seq"] if f > 1) <= 9 < max(c["seq"]), c["name"]
-    assert len({c["name"] for c in cs}) == len(cs) == 37
+    assert len({c["name"] for c in cs}) == len(cs) == 37 + 15
+    assert [c["seed"] for c in cs] == list(range(pm.SEED, pm.SEED + len(cs))) and not any(pm.is_fast(c) for c in cs[:37]) and all(pm.is_fast(c) and c["family"] == "fast" for c in cs[37:])
+    # quality 7, behind the 37: kinds of their own, sequences of SEQS, the two-output cases reach every shape
+    assert [(c["sr"], c["kb"]) for c in by("fast_stereo")] == pm.FAST_STEREO == [(44100, 128), (44100, 320), (32000, 160), (22050, 64), (44100, 48)]
+    assert [(c["sr"], c["kb"]) for c in by("fast_mono")] == pm.FAST_MONO and pm.FAST_MONO[:3] == [(44100, 128), (22050, 64), (44100, 32)] and all(c["ch"] == 1 for c in by("fast_mono"))
+    assert [(c["sr"], c["kb"]) for c in by("fast_joint")] == [(44100, 128), (22050, 64)]
+    for kind in ("fast_protect", "fast_f32gain", "fast_downmix", "fast_resv_stereo"):
+        assert [(c["ch"], c["sr"], c["kb"]) for c in by(kind)] == [(2, 44100, 128)], kind
+    assert by("fast_protect")[0]["opts"] == dict(pm.FLAGS, quality=7) and by("fast_resv_stereo")[0]["resv"] == "helpers" and tuple(by("fast_resv_stereo")[0]["seq"]) == pm.RESV_SHAPES["helpers"][1]
+    assert all(tuple(c["seq"]) in map(tuple, pm.SEQS) for c in cs[37:] if not c["resv"])
+    assert {f for c in cs if c["kind"] in pm.FAST_TWO_OUT for f in c["seq"]} == set(pm.SHAPES) | {0}
+    assert set(pm.ENVS) == {"default", "pair0", "noframe", "both", "nofast", "grid1"} and len(pm.SWITCHES) == 4 and all(set(e) <= set(pm.SWITCHES) for e in pm.ENVS.values())
+    assert pm.ENVS["nofast"] == {"LAMEJS_HIP_NO_FAST_QUANT": "1"} and pm.ENVS["grid1"] == {"LAMEJS_HIP_QUANT_GRID_MAX": "1", "LAMEJS_HIP_PAIR_MAX_FRAMES": "0"}
+    assert [c["name"] for c in pm.select(cs, "grid1") if not pm.is_fast(c)] == [c["name"] for c in cs if c["family"] == "mpeg1" and c["kind"] in ("stereo", "mono")]
     assert all(max(c["seq"]) <= 17 for c in pm.for_wavesim(cs))
+
+
+def test_fast_cases_reach_every_form_of_the_fast_kernel(sims):
+    """(PAIR, SKIP) of g_quant_fast by the rule of lhip_tables.h (TableSet::skip_tail) on each case's own blob.  g_quant_fast<0, 0> is reachable, and by
+    common configurations: a one-channel stream's lowpass lies higher than a two-channel one's, so one channel at 44100/128, 22050/64 and 32000/96 -- and the
+    downmix -- keeps the polyphase bands 28..31.  48000/320 does NOT: every one-channel 48 kHz blob has skip_tail true.  Two channels keep them at 44100/320,
+    32000/160 and 22050/64.  The case list must launch all four forms, each in a 150-frame call."""
+    import lamejs_amd
+    cs = pm.cases()
+    form = {(c["kind"], c["sr"], c["kb"]): pm.fast_form(c) for c in cs if pm.is_fast(c) and not c["resv"]}
+    assert form == {("fast_stereo", 44100, 128): (1, 1), ("fast_stereo", 44100, 320): (1, 0), ("fast_stereo", 32000, 160): (1, 0), ("fast_stereo", 22050, 64): (1, 0),
+                    ("fast_stereo", 44100, 48): (1, 1), ("fast_mono", 44100, 128): (0, 0), ("fast_mono", 22050, 64): (0, 0), ("fast_mono", 44100, 32): (0, 1),
+                    ("fast_mono", 32000, 96): (0, 0), ("fast_joint", 44100, 128): (1, 1), ("fast_joint", 22050, 64): (1, 0), ("fast_protect", 44100, 128): (1, 1),
+                    ("fast_f32gain", 44100, 128): (1, 1), ("fast_downmix", 44100, 128): (0, 0)}
+    assert {pm.fast_form(c) for c in cs if pm.is_fast(c) and not c["resv"] and 150 in c["seq"]} == {(1, 1), (1, 0), (0, 1), (0, 0)}
+    for kb in (128, 256, 320):
+        af = pm.blob_array(lamejs_amd.tables_blob(1, 48000, kb, quality=7), "amp_filter", "f")
+        assert all(float(af[b]) < 1e-12 for b in (28, 29, 30, 31)), kb
+
+
+def test_oracle_blob_keeps_the_quality(sims):
+    """Where the oracle's blob is not the encoder's (Float32 with gains, the downmix) it is still a quality-7 blob: the six switches of the fast mode."""
+    import lamejs_amd
+    from protection_cases import cfg_entry
+    from quality_cases import SWITCHES
+    for c in pm.cases():
+        ob, eb = pm.oracle_blob(c), lamejs_amd.tables_blob(c["ch"], c["sr"], c["kb"], **c["opts"])
+        assert [cfg_entry(ob, k)[1] for k in SWITCHES] == [cfg_entry(eb, k)[1] for k in SWITCHES], c["name"]
+        assert (cfg_entry(ob, "noise_shaping")[1] == 0 and cfg_entry(ob, "use_best_huffman")[1] == 0) == pm.is_fast(c), c["name"]
+
+
+def test_oracle_reproduces_the_reference_at_quality_7(sims):
+    """The fast cases take their expectations from the unchanged oracle on a quality-7 blob.  That is a reference only because it writes the unmodified
+    reference's bytes (tests/golden/golden_quality.json): two channels, one channel, joint stereo, protected frames, 22050 Hz, integer resampling."""
+    import quality_cases as qc
+    G = {c["name"]: c for c in qc.goldens()}
+    for name in ("q7_stereo_44100_128", "q7_mono_44100_64", "q7_joint_mixed_128", "q7_protect_128", "q7_stereo_22050_48", "q7_stereo_48000_320", "q7_stereo_44100_48_resample_int"):
+        assert G[name]["quality"] == 7 and qc.oracle_takes(G[name]) and qc.oracle_reproduces(G[name]), name
 
 
 def test_plan_calls_completes_the_frames_it_plans(sims):
@@ -122,24 +179,40 @@ def test_material_is_not_trivial(sims):
 def _run(backend, env_name, limit, cs):
     status, recs, text, _ = pm.run_child(env_name, backend, limit)
     assert status == 0, (status, text)
+    print(backend, env_name, recs[-1])
     bad = pm.check_records(cs, recs, env_name, backend, 256)
     assert bad == [], "\n".join(bad[:40])
     return recs
 
 
-@pytest.mark.parametrize("env_name", ["default", "both"])
+def _fast_batches(recs):
+    return [r for r in recs if r.get("kind", "").startswith("fast_") and "SEPARATE" in r.get("paths", ()) and not r["kind"].startswith("fast_resv")]
+
+
+@pytest.mark.parametrize("env_name", ["default", "both", "nofast"])
 def test_hostsim_matrix(sims, env_name):
-    """Full shapes on the scalar simulation (about 10 000 frames, 17 s here; the limit only ends a child that hangs)."""
+    """Full shapes on the scalar simulation (the limit only ends a child that hangs)."""
     recs = _run("hostsim", env_name, 600, pm.cases())
     assert not any("QUANT_PAIR" in r.get("paths", ()) for r in recs)
+    fast = _fast_batches(recs)
+    assert fast and all(("QUANT_FAST" in r["paths"]) == (env_name != "nofast") for r in fast)
+    assert {r["frames"] for r in fast if r["kind"] in pm.FAST_TWO_OUT} >= set(pm.SHAPES) - {1}
 
 
-@pytest.mark.parametrize("env_name", ["default", "pair0"])
+@pytest.mark.parametrize("env_name", ["default", "pair0", "nofast"])
 def test_wavesim_matrix(sims, env_name):
-    """Shapes capped at 17 frames on the wave simulation: both wave programs of the two-channel quantization."""
-    recs = _run("wavesim", env_name, 1200, pm.for_wavesim(pm.cases()))
+    """Shapes capped at 17 frames on the wave simulation: both wave programs of the two-channel quantization, and g_quant_fast's workgroup of
+    pairs / of single waves -- one workgroup, as LAMEJS_HIP_QUANT_GRID_MAX=1 makes the device's."""
+    recs = _run("wavesim", env_name, 1800, pm.for_wavesim(pm.cases()))
     two = [r for r in recs if r.get("kind") in pm.TWO_OUT and r.get("frames", 0) >= 2]
     if env_name == "pair0":
         assert two and all("QUANT_PERSISTENT" in r["paths"] for r in two)
     else:
         assert {"QUANT_PAIR", "QUANT_PERSISTENT"} <= {p for r in two for p in r["paths"]}
+    fast = _fast_batches(recs)
+    if env_name == "nofast":
+        assert fast and {"QUANT_PAIR", "QUANT_PERSISTENT"} <= {p for r in fast for p in r["paths"]} and not any("QUANT_FAST" in r["paths"] for r in fast)
+    else:
+        assert fast and all("QUANT_FAST" in r["paths"] and r["launch"]["wg"] == 1 and r["launch"]["waves"] == 8 for r in fast)
+        need = pm.check_one_workgroup(recs, env_name, max_shape=17)
+        assert [b for b in need if env_name == "pair0" or "g_quant calls" not in b] == [], need
