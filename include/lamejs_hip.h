@@ -69,6 +69,11 @@
  * bytes) cannot hold sideinfo_len + 156 bytes, and for a stream that resamples by a non-integer ratio.  State blobs do not carry the totals: lhip_info_tag
  * on a stream moved with lhip_seek or lhip_state_set returns -4.
  *
+ * Output sample rate and filters (extension).  A blob built with { outSampleRate, lowpass, lowpassWidth, highpass, highpassWidth } (tables.js) carries the
+ * reference core's gfp.out_samplerate, lowpassfreq, lowpasswidth, highpassfreq and highpasswidth as it carries the automatic choice: in out_samplerate,
+ * version, mode_gr, brate, the resampler tables and the 32 band factors of amp_filter (Lame.js:470-558, the highpass half included).  No entry and no
+ * configuration field is added.  lhip_create returns -3 with a message for an amp_filter value that is not finite or lies outside [0, 1].
+ *
  * Semantics preserved: any chunking of the same sample stream yields the same bytes; a call
  * returns the bytes of all whole frames completed by that call (possibly 0); errors are negative
  * return codes mirroring the reference (-1 output buffer too small, -3 bad handle, -4 internal/device

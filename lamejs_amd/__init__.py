@@ -184,7 +184,8 @@ def _gain_text(g) -> str:
 
 def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, reservoir: bool = False, fractional_resample: bool = False,
                 downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False, copyright: bool = False, original: bool = True,
-                private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False, quality: int = 3) -> bytes:
+                private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False, quality: int = 3,
+                out_samplerate=None, lowpass=None, lowpass_width=None, highpass=None, highpass_width=None) -> bytes:
     """The LHTB table blob for a configuration.
 
     Built by the host-side JavaScript ``lamejs_amd/js/tables.js`` (so every transcendental comes
@@ -205,7 +206,24 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     ``quality``: 3 (the reference wrapper's setting) or 7, LAME's ``-f`` (``{ quality }`` of tables.js: the psychoacoustic model still decides block
     switching and mid/side, the quantization is the bin search alone); 8 is encoded as 7, as the reference's core does.  At 3 the blob is the bytes
     it always was.
+    ``out_samplerate``, ``lowpass``, ``lowpass_width``, ``highpass``, ``highpass_width`` (``{ outSampleRate, lowpass, lowpassWidth, highpass, highpassWidth }`` of
+    tables.js): the reference core's ``gfp.out_samplerate``, ``lowpassfreq``, ``lowpasswidth``, ``highpassfreq`` and ``highpasswidth`` -- LAME's ``--resample``,
+    ``--lowpass``, ``--lowpass-width``, ``--highpass``, ``--highpass-width`` -- as whole numbers of Hz.  ``out_samplerate``: one of the nine MPEG rates, the input
+    rate or the input rate divided by a whole number; ``lowpass``: at least 1, or -1 for no lowpass (without ``out_samplerate`` it also chooses the output
+    rate, as the core does); the widths: at least 0, a cosine transition instead of the hard edge; ``highpass``: at least 1 and not below the stream's minimum
+    (tables.js names it).  A value of another type raises ``ValueError``, as does whatever tables.js refuses with a ``RangeError``.  No blob entry is
+    added: without the five options the blob is the bytes it always was.
     """
+    filt = []
+    for word, name, v, lo, minus_one in (("outrate", "out_samplerate", out_samplerate, 1, False), ("lowpass", "lowpass", lowpass, 1, True), ("lowpasswidth", "lowpass_width", lowpass_width, 0, False),
+                                         ("highpass", "highpass", highpass, 1, False), ("highpasswidth", "highpass_width", highpass_width, 0, False)):
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (v >= lo or (minus_one and v == -1)):
+            raise ValueError(f"{name} must be a whole number of Hz >= {lo}" + (", or -1" if minus_one else ""))
+        filt.append(f"{word}={int(v)}")
+    if highpass_width is not None and highpass is None:
+        raise ValueError("highpass_width needs highpass")
     if isinstance(quality, bool) or quality not in (3, 7, 8):
         raise ValueError("quality must be 3, 7 or 8 (8 is encoded as 7)")
     quality = 7 if quality == 8 else int(quality)
@@ -225,6 +243,7 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
     mix += ["infoTag"] if info_tag else []
     mix += ["replayGain"] if replay_gain else []
     mix += [f"quality={quality}"] if quality != 3 else []
+    mix += filt
     f = _TABLE_DIR / f"t_{channels}_{samplerate}_{kbps}{'_joint' if joint else ''}{'_resv' if reservoir else ''}{'_frac' if frac else ''}{''.join('_' + m.replace('=', '') for m in mix)}.bin"
     if not f.exists() or not blob_is_current(f.read_bytes()):      # a cached blob made by another version of its generator is stale
         _TABLE_DIR.mkdir(exist_ok=True)
@@ -233,6 +252,8 @@ def tables_blob(channels: int, samplerate: int, kbps: int, joint: bool = False, 
                            check=True, capture_output=True, text=True)
         except (OSError, subprocess.CalledProcessError) as e:  # pragma: no cover
             msg = getattr(e, "stderr", "") or str(e)
+            if filt and "RangeError" in msg:           # a filter setting tables.js refuses: the caller's value, not a missing blob
+                raise ValueError(next((ln for ln in msg.splitlines() if "RangeError" in ln), msg).strip())
             if isinstance(e, OSError) and f.exists():      # no node on this machine: use the blob that was shipped
                 return f.read_bytes()
             raise LhipError(f"no table blob for ({channels},{samplerate},{kbps}{',joint' if joint else ''}) and node could not build it: {msg}")
@@ -279,7 +300,8 @@ class Mp3Encoder:
 
     def __init__(self, channels: int = 1, samplerate: int = 44100, kbps: int = 128, device: int = -1, lib=None, joint: bool = False, reservoir: bool = False,
                  fractional_resample: bool = False, downmix: bool = False, scale=None, scale_left=None, scale_right=None, protect: bool = False,
-                 copyright: bool = False, original: bool = True, private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False, quality: int = 3):
+                 copyright: bool = False, original: bool = True, private_bit: bool = False, emphasis: int = 0, info_tag: bool = False, replay_gain: bool = False, quality: int = 3,
+                 out_samplerate=None, lowpass=None, lowpass_width=None, highpass=None, highpass_width=None):
         """``joint`` (extension, not in the reference's wrapper): encode two channels in the reference's joint-stereo mode --
         per frame mid/side or left/right, as its encoder core decides when asked for MPEGMode.JOINT_STEREO.
         ``reservoir`` (extension): encode with the bit reservoir in use (the reference's wrapper disables it, index.js:108); the frames
@@ -302,12 +324,16 @@ class Mp3Encoder:
         core's ReplayGain analysis does; ``replay_gain()`` reports the track gain, and with ``info_tag`` the tag's radio field carries it.
         ``quality`` (extension): 3, the reference wrapper's setting, or 7 -- LAME's ``-f``, the reference core's fast mode: block switching and mid/side as
         always, quantization by the bin search alone (a batch of such streams is quantized by the kernel g_quant_fast).  8 is encoded as 7; any other
-        value raises ``ValueError``."""
+        value raises ``ValueError``.
+        ``out_samplerate``, ``lowpass``, ``lowpass_width``, ``highpass``, ``highpass_width`` (extension): the reference core's output sample rate and polyphase
+        filter settings in whole Hz (``tables_blob``) -- ``Mp3Encoder(2, 44100, 96, out_samplerate=44100)`` is a stream without resampling.  A value that is no
+        whole number, a highpass below the stream's minimum or not below the lowpass, upsampling and a non-integer ratio raise ``ValueError``."""
         self._lib = lib or load_library()
         self.channels, self.samplerate, self.kbps = int(channels), int(samplerate), int(kbps)
         self._resv = bool(reservoir)
         blob = tables_blob(self.channels, self.samplerate, self.kbps, joint, reservoir, fractional_resample, downmix, scale, scale_left, scale_right,
-                           protect, copyright, original, private_bit, emphasis, info_tag, replay_gain, quality)
+                           protect, copyright, original, private_bit, emphasis, info_tag, replay_gain, quality,
+                           out_samplerate, lowpass, lowpass_width, highpass, highpass_width)
         cfg = _Config(self.channels, self.samplerate, self.kbps, device)
         h = ctypes.c_void_p()
         buf = ctypes.create_string_buffer(blob, len(blob))

@@ -254,6 +254,9 @@ static bool derive_index_tables(TableSet& ts, void* stream) {
     extra.resize(amp_at + 64);
     {
         const float* h_af = (const float*)host_arr("amp_filter");
+        // the band filter (lowpass and highpass: { lowpass, lowpassWidth, highpass, highpassWidth }): products of two cosine ramps, so every value lies in [0, 1]
+        for (int band = 0; band < 32; band++)
+            if (!std::isfinite(h_af[band]) || h_af[band] < 0.f || h_af[band] > 1.f) { set_err("band filter: amp_filter[" + std::to_string(band) + "] is not a finite value in [0, 1]"); ts.bad_option = true; return false; }
         ts.skip_tail = (double)h_af[28] < 1e-12 && (double)h_af[29] < 1e-12 && (double)h_af[30] < 1e-12 && (double)h_af[31] < 1e-12;      // (k_fb.h: such a band is zero-filled)
         const int32_t* h_order = (const int32_t*)host_arr("mdct_order");
         double amp[32];

@@ -47,6 +47,14 @@
  * decisions as always, the quantization of a granule is the bin search for its step size alone -- no noise shaping, no Huffman region search -- so the
  * bytes are those of the reference core with gfp.quality = 7, and a batch is quantized by a kernel of its own (g_quant_fast).  8 is encoded as 7, as the
  * core does; 3 is the default; any other value is a RangeError.  With every option above, encodeBatch() of encoders of both qualities included.
+ * Extension { outSampleRate, lowpass, lowpassWidth, highpass, highpassWidth }: the reference core's gfp.out_samplerate, lowpassfreq, lowpasswidth, highpassfreq
+ * and highpasswidth (LAME's --resample, --lowpass, --lowpass-width, --highpass, --highpass-width), whole numbers of Hz.  outSampleRate is one of the nine MPEG
+ * rates, the input rate or the input rate divided by a whole number: new Mp3Encoder(2, 44100, 96, { outSampleRate: 44100 }) is a plain stream without
+ * resampling (the default picks 32000 Hz there, a non-integer ratio).  lowpass replaces the bitrate's band limit (-1: no lowpass) and, without outSampleRate,
+ * chooses the output rate as the core does; the widths give the filters a cosine transition instead of a hard edge.  A highpass below the stream's minimum
+ * (about 480 Hz at 44.1 kHz), at or above the lowpass, a width without its highpass, upsampling, a non-integer ratio and any value that is not a whole
+ * number are RangeErrors.  With every option above, encodeBatch() of encoders with different settings included; not with a { fractionalResample } stream
+ * that resamples by a non-integer ratio.
  * Extension { fractionalResample: true }: the 49 (channels, sample rate, kbps) triples the reference resamples by a non-integer ratio -- refused
  * by default, because the reference feeds itself NaN samples there once a call is long enough -- are accepted as call-sequence streams: every
  * encodeBuffer() gives the reference's bytes for the same sequence of call lengths; a call longer than the reference consumes whole throws
@@ -80,7 +88,8 @@ function tablesBlob(channels, samplerate, kbps, opts) {
     const key = [channels, samplerate, kbps, opts && opts.jointStereo ? 1 : 0, opts && opts.reservoir ? 1 : 0, opts && opts.fractionalResample ? 1 : 0,
         opts && opts.downmix ? 1 : 0, opts ? String(opts.scale) : '', opts ? String(opts.scaleLeft) : '', opts ? String(opts.scaleRight) : '',
         opts ? ['protect', 'copyright', 'original', 'privateBit', 'emphasis'].map((k) => String(opts[k])).join(',') : '', opts && opts.infoTag ? 1 : 0, opts && opts.replayGain ? 1 : 0,
-        opts ? typeof opts.quality + String(opts.quality) : ''].join('|');     /* (quality with its type: '7' is refused, not served 7's blob; pendingFrames is host-side only) */
+        opts ? typeof opts.quality + String(opts.quality) : '',
+        opts ? ['outSampleRate', 'lowpass', 'lowpassWidth', 'highpass', 'highpassWidth'].map((k) => typeof opts[k] + String(opts[k])).join(',') : ''].join('|');     /* (quality and the filter options with their type: '7' is refused, not served 7's blob; pendingFrames is host-side only) */
     let blob = blobCache.get(key);
     if (!blob) { blob = tables.buildBlob(channels, samplerate, kbps, opts).blob; blobCache.set(key, blob); }
     return blob;

@@ -10,7 +10,7 @@
  * Behaviour restated (not copied) from the reference's one-time init:
  *   index.js:100-111        fixed Mp3Encoder configuration
  *   Lame.js:747-1371        lame_init_params (CBR, vbr_off branch only)
- *   Lame.js:470-558         polyphase low-pass amplitudes (amp_filter)
+ *   Lame.js:470-558         polyphase high-pass and low-pass amplitudes (amp_filter)
  *   Lame.js:560-690         quality map (quality 3; 7 with { quality: 7 })
  *   Presets.js:226-358      ABR preset row applied for CBR
  *   QuantizePVT.js:247-414  ATH per sfb, pow43/adj43/ipow20/pow20, long/shortfact
@@ -89,16 +89,62 @@ function resolveParams(channels, samplerate, kbps, opts) {
     p.in_samplerate = samplerate;
     let brate = kbps;
 
-    /* lowpass from bitrate (Lame.js:838-885) */
-    let lowpass = C.lowpass_freq_map[nearestBitrateFullIndex(brate)][1];
-    if (p.mode == MODE_MONO) lowpass *= 1.5;
-    let lowpassfreq = lowpass | 0;
-    if (2 * lowpassfreq > samplerate) lowpassfreq = samplerate / 2;
-    const out_samplerate = suggestedSampleFreq(lowpassfreq | 0, samplerate);
+    /* extension { outSampleRate, lowpass, lowpassWidth, highpass, highpassWidth }: gfp.out_samplerate, lowpassfreq, lowpasswidth, highpassfreq and
+     * highpasswidth of the reference's core (LAME's --resample, --lowpass, --lowpass-width, --highpass, --highpass-width), which its wrapper leaves at
+     * lame_init's values (0, 0, -1, 0, -1: Lame.js:147-150).  Whole numbers of Hz; lowpass -1 switches the filter off (LAME's convention) */
+    const fopt = (k, min, what, minusOne) => {
+        if (!opts || opts[k] === undefined || opts[k] === null) return null;
+        const v = opts[k];
+        if (typeof v != 'number' || !Number.isInteger(v) || !(v >= min || (minusOne && v === -1)))
+            throw new RangeError('lamejs_amd: { ' + k + ' } must be ' + what);
+        return v;
+    };
+    const userOut = fopt('outSampleRate', 1, 'one of the MPEG sample rates 8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000');
+    const userLow = fopt('lowpass', 1, 'a whole number of Hz >= 1, or -1 (no lowpass)', true);
+    const lowpasswidth = fopt('lowpassWidth', 0, 'a whole number of Hz >= 0');
+    const highpassfreq = fopt('highpass', 1, 'a whole number of Hz >= 1');
+    const highpasswidth = fopt('highpassWidth', 0, 'a whole number of Hz >= 0');
+    if (highpasswidth !== null && highpassfreq === null)
+        throw new RangeError('lamejs_amd: { highpassWidth } needs { highpass } (the reference ignores a width without a frequency)');
+    if (userOut !== null) {
+        if (![48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000].includes(userOut))
+            throw new RangeError('lamejs_amd: { outSampleRate } must be one of the MPEG sample rates 8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000');
+        if (userOut > samplerate) throw new RangeError('lamejs_amd: { outSampleRate: ' + userOut + ' } is above the input rate ' + samplerate + ' (upsampling is not supported)');
+        if (samplerate % userOut != 0)
+            throw new RangeError('lamejs_amd: { outSampleRate: ' + userOut + ' } is not the input rate ' + samplerate + ' divided by a whole number (the ratio ' + samplerate / userOut +
+                ' is not supported, with or without { fractionalResample })');
+    }
+    p.filter_options = (userOut !== null || userLow !== null || lowpasswidth !== null || highpassfreq !== null) ? 1 : 0;
+
+    /* lowpass from bitrate (Lame.js:838-885), unless the caller set one */
+    let lowpassfreq;
+    if (userLow === null) {
+        let lowpass = C.lowpass_freq_map[nearestBitrateFullIndex(brate)][1];
+        if (p.mode == MODE_MONO) lowpass *= 1.5;
+        lowpassfreq = lowpass | 0;
+    } else lowpassfreq = userLow;
+    /* Lame.js:887-896: the output rate follows from the lowpass only where the caller set none */
+    let out_samplerate = userOut;
+    if (out_samplerate === null) {
+        if (2 * lowpassfreq > samplerate) lowpassfreq = samplerate / 2;
+        out_samplerate = suggestedSampleFreq(lowpassfreq | 0, samplerate);
+    }
     lowpassfreq = Math.min(20500, lowpassfreq);
     lowpassfreq = Math.min(out_samplerate / 2, lowpassfreq);
     p.out_samplerate = out_samplerate;
     p.lowpassfreq = lowpassfreq;
+    if (highpassfreq !== null) {
+        /* Lame.js:508-515: below this the reference disables the highpass with a warning -- through System.err, which it does not define: it throws */
+        const top = highpassfreq + Math.max(highpasswidth === null ? -1 : highpasswidth, 0);
+        if (2. * top / out_samplerate < .9 * (.75 / 31.0)) {
+            let min = 1;
+            while (2. * min / out_samplerate < .9 * (.75 / 31.0)) min++;
+            throw new RangeError('lamejs_amd: { highpass: ' + highpassfreq + ' } is too low for a stream of ' + out_samplerate + ' Hz: highpass + highpassWidth must be at least ' + min + ' Hz');
+        }
+        /* a highpass at or above the lowpass leaves no band: the reference would encode silence */
+        if (lowpassfreq > 0 && !(top < lowpassfreq))
+            throw new RangeError('lamejs_amd: { highpass } + { highpassWidth } = ' + top + ' Hz must lie below the lowpass, ' + lowpassfreq + ' Hz');
+    }
 
     /* resampler set-up (Lame.js:943, 1719-1763).  By default only integer ratios are in the envelope: for any other ratio the
      * reference's filter_l / 2 is 15.5, and once a fill pass delivers a whole frame its buffer positions become fractional, typed-array
@@ -117,6 +163,9 @@ function resolveParams(channels, samplerate, kbps, opts) {
                 ' without the option { fractionalResample: true } (call-sequence-exact, calls of limited length)');
         if (!intratio && opts.reservoir)
             throw new Error('lamejs_amd: { fractionalResample } and { reservoir } cannot be combined');
+        if (!intratio && p.filter_options)
+            throw new Error('lamejs_amd: { fractionalResample } cannot be combined with { lowpass, lowpassWidth, highpass, highpassWidth } where the stream resamples by a non-integer ratio' +
+                ' ({ outSampleRate } gives such a configuration an integer ratio)');
         const gcd = (i, j) => (j != 0 ? gcd(j, i % j) : i);
         let bpc = out_samplerate / gcd(out_samplerate, samplerate);
         if (bpc > 320) bpc = 320;                                            /* LameInternalFlags.BPC */
@@ -168,11 +217,23 @@ function resolveParams(channels, samplerate, kbps, opts) {
     }
     p.brate = brate;
 
-    /* polyphase lowpass: amp_filter (Lame.js:1011-1040, 470-558); no highpass */
-    let lowpass2 = 2. * lowpassfreq, lowpass1 = (1 - 0.00) * 2. * lowpassfreq;
-    lowpass1 /= out_samplerate; lowpass2 /= out_samplerate;
+    /* polyphase highpass and lowpass: amp_filter (Lame.js:1004-1040, 470-558) */
+    let highpass1 = 0, highpass2 = 0, lowpass1 = 0, lowpass2 = 0;
+    if (highpassfreq !== null) {
+        highpass1 = 2. * highpassfreq;
+        highpass2 = (highpasswidth !== null) ? 2. * (highpassfreq + highpasswidth) : (1 + 0.00) * 2. * highpassfreq;
+        highpass1 /= out_samplerate; highpass2 /= out_samplerate;
+    }
+    if (lowpassfreq > 0) {
+        lowpass2 = 2. * lowpassfreq;
+        if (lowpasswidth !== null) {
+            lowpass1 = 2. * (lowpassfreq - lowpasswidth);
+            if (lowpass1 < 0) lowpass1 = 0;
+        } else lowpass1 = (1 - 0.00) * 2. * lowpassfreq;
+        lowpass1 /= out_samplerate; lowpass2 /= out_samplerate;
+    }
     {
-        let lowpass_band = 32, minband = 999;
+        let lowpass_band = 32, minband = 999, highpass_band = -1, maxband = -1;
         if (lowpass1 > 0) {
             for (let band = 0; band <= 31; band++) {
                 const freq = band / 31.0;
@@ -182,15 +243,23 @@ function resolveParams(channels, samplerate, kbps, opts) {
             lowpass1 = ((minband == 999 ? lowpass_band : minband) - .75) / 31.0;
             lowpass2 = lowpass_band / 31.0;
         }
+        if (highpass2 > 0) {             /* (never below .9 * .75 / 31 here: refused above) */
+            for (let band = 0; band <= 31; band++) {
+                const freq = band / 31.0;
+                if (freq <= highpass1) highpass_band = Math.max(highpass_band, band);
+                if (highpass1 < freq && freq < highpass2) maxband = Math.max(maxband, band);
+            }
+            highpass1 = highpass_band / 31.0;
+            highpass2 = ((maxband == -1 ? highpass_band : maxband) + .75) / 31.0;
+        }
+        const filter_coef = (x) => (x > 1.0 ? 0.0 : (x <= 0.0 ? 1.0 : Math.cos(Math.PI / 2 * x)));      /* Lame.js:239-246 */
         p.amp_filter = f32(32);
         for (let band = 0; band < 32; band++) {
             const freq = band / 31.0;
-            let fc2 = 1.0;
-            if (lowpass2 > lowpass1) {
-                const x = (freq - lowpass1) / (lowpass2 - lowpass1 + 1e-20);
-                fc2 = x > 1.0 ? 0.0 : (x <= 0.0 ? 1.0 : Math.cos(Math.PI / 2 * x));
-            }
-            p.amp_filter[band] = 1.0 * fc2;
+            let fc1 = 1.0, fc2 = 1.0;
+            if (highpass2 > highpass1) fc1 = filter_coef((highpass2 - freq) / (highpass2 - highpass1 + 1e-20));
+            if (lowpass2 > lowpass1) fc2 = filter_coef((freq - lowpass1) / (lowpass2 - lowpass1 + 1e-20));
+            p.amp_filter[band] = (fc1 * fc2);
         }
     }
 
@@ -783,13 +852,18 @@ module.exports = { buildBlob, resolveParams, buildTables, packBlob, sourceHash, 
 
 if (require.main === module) {
     /* CLI: node tables.js <channels> <samplerate> <kbps> <out.bin> [joint] [reservoir] [fracresample] [downmix] [scale=G] [scaleLeft=G] [scaleRight=G]
-     *      [protect] [copyright] [original=0|1] [privateBit] [emphasis=E] [infoTag] [replayGain] [quality=3|7|8] */
+     *      [protect] [copyright] [original=0|1] [privateBit] [emphasis=E] [infoTag] [replayGain] [quality=3|7|8]
+     *      [outrate=HZ] [lowpass=HZ|-1] [lowpasswidth=HZ] [highpass=HZ] [highpasswidth=HZ] */
     const [ch, sr, kb, out] = process.argv.slice(2), flags = process.argv.slice(6);
     const opts = { jointStereo: flags.includes('joint'), reservoir: flags.includes('reservoir'), fractionalResample: flags.includes('fracresample') };
     if (flags.includes('downmix')) opts.downmix = true;
     for (const f of flags) { const m = /^(scale|scaleLeft|scaleRight)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
     for (const k of ['protect', 'copyright', 'privateBit', 'infoTag', 'replayGain']) if (flags.includes(k)) opts[k] = true;
     for (const f of flags) { const m = /^(original|emphasis|quality)=(.+)$/.exec(f); if (m) opts[m[1]] = Number(m[2]); }
+    {
+        const W = { outrate: 'outSampleRate', lowpass: 'lowpass', lowpasswidth: 'lowpassWidth', highpass: 'highpass', highpasswidth: 'highpassWidth' };
+        for (const f of flags) { const m = /^(outrate|lowpass|lowpasswidth|highpass|highpasswidth)=(.+)$/.exec(f); if (m) opts[W[m[1]]] = Number(m[2]); }
+    }
     const r = buildBlob(+ch, +sr, +kb, opts);
     require('fs').writeFileSync(out, r.blob);
     console.log('wrote', out, r.blob.length, 'bytes');
