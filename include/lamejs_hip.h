@@ -350,7 +350,8 @@ int lhip_debug_ingest(int format, int channels, const void* bytes, size_t nsampl
 /* Debug/test taps (tests only): copy intermediate results of the most recent batch to the host.
  * what: 0 xr [granule][ch][576] f32, 1 blocktype [granule][ch] i32, 2 E [granule][psy ch][122] f32 (psy ch = ch, or L R mid side in joint stereo; thresholds
  * handed to the quantizer for that granule), 3 ath_adjust [frame] f64, 4 side records (struct GrSide); simulation libraries only: 10 two i64, the
- * evaluations of the quantization search this process has made without / with the last round of pairs (lines 512..575 all zero / not).
+ * evaluations of the quantization search this process has made without / with the last round of pairs (lines 512..575 all zero / not); 12 three i64, the calc_noise calls this process has made with 7 / with 9 / with 3
+ * spectrum lines per lane (counted by the 64-lane simulation; the one-lane simulation reports zeros).
  * 11 (every library; needs no batch to have run): eight i32, the speculative quantization launch of the calling thread's most recent batch -- [0] workgroups
  * launched, [1] waves per workgroup, [2] frame slots, [3] the kernel (1 g_quant_fast, 2 g_quant_pair, 3 g_quant), [4] [5] its PAIR and SKIP template arguments
  * (g_quant_pair: PAIR 1, g_quant: 0), [6] [7] zero; all zero when the batch launched none (one-frame program, bit reservoir).  The wave simulation reports the

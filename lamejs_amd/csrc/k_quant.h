@@ -101,9 +101,11 @@ struct alignas(16) QuantTabs {
     struct PlanEnt { uint32_t d0, d1, pw; } plan[30];
     // scale_bitcount candidates (Takehiro.js:980-1030): row k = slen1_n | slen2_n << 8 | scale_long << 16 | scale_short << 24
     uint32_t sbc[16];
-    // calc_noise's systolic fold (lane l owns the lines 9 l .. 9 l + 8): bit k = line 9 l + k is the first of its scalefactor band,
-    // bit 16 + k = it is the last one; [0] long blocks, [1] short blocks.  wpre: widest band among bands 0 .. b (long / short).
+    // calc_noise's systolic fold (lane l owns the lines n l .. n l + n - 1, n = noise_nln: 7 or 9, Tables::noise_nln): bit k = line n l + k is the
+    // first of its scalefactor band, bit 16 + k = it is the last one; bits 12 + k and 28 + k: the same for the short window's lines 3 l + k, k < 3;
+    // [0] long blocks, [1] short blocks.  wpre: widest band among bands 0 .. b (long / short).
     uint32_t fold_marks[2][64];
+    int32_t noise_nln;
     uint16_t wpre_long[24], wpre_short[40];
     // analog silence (Quantize.js:147-202): pseudo-band borders above sfb21 / sfb12, their ATH values ([0..5] long, [6..11] short) and the
     // two band factors they are scaled with
@@ -153,6 +155,7 @@ LHIP_DEV void q_load_tabs(const Tables& T, QuantTabs& Q, int tid, int nthr) {
     for (int e = tid; e < PSFB21 + PSFB12; e += nthr) Q.ath_psfb[e] = e < PSFB21 ? T.ATH_psfb21[e] : T.ATH_psfb12[e - PSFB21];
     if (tid == 0) { Q.fact_psfb[0] = T.longfact[21]; Q.fact_psfb[1] = T.shortfact[12]; }
     for (int e = tid; e < 2 * 64; e += nthr) Q.fold_marks[e >> 6][e & 63] = (uint32_t)T.fold_marks[e];
+    if (tid == 0) Q.noise_nln = T.noise_nln;
     for (int e = tid; e < 24; e += nthr) Q.wpre_long[e] = (uint16_t)T.wpre[e];
     for (int e = tid; e < 40; e += nthr) Q.wpre_short[e] = (uint16_t)T.wpre[24 + e];
 }
@@ -1078,6 +1081,86 @@ LHIP_DEV int q_count_bits_rounds(const Tables& T, GI& g, const int32_t* scalefac
     return q_count_bits<NPL>(T, g, scalefac, ix, use_pn, pn, asg, lane, L, Q);
 }
 
+#if defined(LHIP_HOSTSIM)
+// how many calc_noise calls ran with 7, with 9 and with 3 lines per lane: lhip_debug_read(12), for the tests that must see the form a configuration takes
+// (the 64-lane simulation counts; the one-lane one has no lanes to share the lines among and reports zeros)
+struct NoiseLineStats { long n7 = 0, n9 = 0, n3 = 0; };
+inline NoiseLineStats& noise_line_stats() { static NoiseLineStats t; return t; }
+#define LHIP_NOISE_LINES_COUNT(f) do { if (lane == 0) __atomic_fetch_add(&noise_line_stats().f, 1L, __ATOMIC_RELAXED); } while (0)
+#else
+#define LHIP_NOISE_LINES_COUNT(f) do { } while (0)
+#endif
+#if LHIP_NL != 1
+// calc_noise's line pass and systolic fold (step 2 of q_calc_noise_, which says how the fold reproduces the reference's sums): the squared
+// errors of the lines 0 .. 64 NLN - 1, NLN consecutive lines per lane, summed per band into L.nsum.  NLN = 9 covers the spectrum.  NLN = 3 is the short
+// window (lines 0..191) of a call whose fresh bands all end at or below line 192 -- the other bands' values come from the cache; its marks sit 12 bits up
+// in the same words of fold_marks.  NLN = 7
+// stops at line 448: q_calc_noise_ reads L.nsum[sfb] for sfb < psymax alone -- 21 long bands or 36 short ones, sfb21_extra being refused -- and
+// Tables::noise_nln is 7 only where every such band ends at or below line 448.  A band cut off by line 448 gets no end mark in
+// QuantTabs::fold_marks (built for the same NLN), so its partial sum is never stored.  (L.nsum's other readers, q_calc_xmin and the
+// perceptual entropies, fill it themselves: fold_band_sums, q_frame_pe.)
+template <int NLN>
+LHIP_DEV void q_noise_band_sums(const Tables& T, const GI& g, const int16_t* ix, int may_big, int maxlen, int lane, QuantLds& L, const QuantTabs& Q,
+                                unsigned long long& tm_) {
+    static_assert(LHIP_NL == 64 && (NLN == 3 || NLN == 7 || NLN == 9), "QuantTabs::fold_marks is laid out for 3 and for 7 or 9 lines on each of 64 lanes");
+    enum { MS = NLN == 3 ? 12 : 0 };                 // the short window's marks sit 12 bits up in the same words
+    if (NLN == 3) LHIP_NOISE_LINES_COUNT(n3); else if (NLN == 7) LHIP_NOISE_LINES_COUNT(n7); else LHIP_NOISE_LINES_COUNT(n9);
+    double tq[NLN], keep[NLN];
+    int lastb[NLN];
+    const uint32_t marks = Q.fold_marks[g.block_type == SHORT_TYPE][lane];
+    const uint8_t* l2s = line2sfb(Q, g.block_type);
+    // Terms are computed for every line below 64 NLN, evaluated band or not: a cached band's sum is never read.
+    // keep[k] = 0 at a band start, 1 elsewhere: fma(sum, keep, t) is `sum + t` or `t` with ONE rounding, i.e.
+    // exactly the reference's `noise += t` (or a fresh sum); no contraction is involved, the fma is explicit.
+    // |xr| - pow43 * step: the product of two Float32 values is exact in f64, so the explicit fma's single rounding is the
+    // reference's (a product, then a difference).
+    // !may_big (the usual case): every quantized value is below QT_N (q_calc_noise_), nothing to clamp; else the clamped look-up is
+    // replaced in the pass that follows
+#define NOISE_TERMS(IDX) _Pragma("unroll") for (int k = 0; k < NLN; k++) { \
+        const int j = NLN * lane + k; \
+        const int bnd = l2s[j]; \
+        const float bstep = L.bstep[bnd]; \
+        const float xa = L.xr[j]; const int iv = ix[j]; \
+        const float pw = Q.pow43[IDX]; \
+        const double x = __builtin_fma(-(double)pw, (double)bstep, d_abs((double)xa)); \
+        tq[k] = x * x; \
+        keep[k] = one_unless_bit(marks, MS + k); \
+        lastb[k] = bnd; \
+    }
+    if (!may_big) { NOISE_TERMS(iv) } else { NOISE_TERMS(iv < QT_N ? iv : QT_N - 1) }
+#undef NOISE_TERMS
+    if (may_big) {                                   // rare: quantized values beyond the part of pow43 staged in LDS
+#pragma unroll
+        for (int k = 0; k < NLN; k++) {
+            const int j = NLN * lane + k;
+            const int iv = ix[j];
+            if (iv >= QT_N) {
+                const double x = __builtin_fma(-(double)T.pow43[iv], (double)L.bstep[lastb[k]], d_abs((double)L.xr[j]));
+                tq[k] = x * x;
+            }
+        }
+    }
+    PH_MARK(L, PH_N_LINES, tm_);
+    const int nsteps = (maxlen + NLN - 1) / NLN + 1;
+    double carry = 0.0;
+    for (int st = 0; st + 1 < nsteps; st++) {
+        double sacc = carry;
+#pragma unroll
+        for (int k = 0; k < NLN; k++) sacc = __builtin_fma(sacc, keep[k], tq[k]);
+        carry = wave_shr1d(sacc, 0.0);
+    }
+    {
+        double sacc = carry;
+#pragma unroll
+        for (int k = 0; k < NLN; k++) { sacc = __builtin_fma(sacc, keep[k], tq[k]); tq[k] = sacc; }   // tq := running sums of the last step
+    }
+#pragma unroll
+    for (int k = 0; k < NLN; k++) if ((marks >> (16 + MS + k)) & 1u) L.nsum[lastb[k]] = tq[k];
+    wave_sync();
+    PH_MARK(L, PH_N_FOLD, tm_);
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // calc_noise (QuantizePVT.js:784-878); distort -> L.distort, cache -> L.pn_*
 // The bands' sums in the reference's line order (f64 sums are order-sensitive) as a systolic fold; all gathers hit LDS.
@@ -1190,63 +1273,12 @@ LHIP_DEV void q_calc_noise_(const Tables& T, const GI& g, const int32_t* scalefa
     //    handed over by lane l-1 (reset at band starts).  One hand-over step extends every band's chain by one
     //    lane, so ceil(longest band / NLN) + 1 steps reproduce the strictly sequential sums exactly, while the
     //    terms themselves are computed once, all lanes busy.
-    enum { NLN = 576 / LHIP_NL };
-    static_assert(NLN == 9, "QuantTabs::fold_marks is laid out for 9 lines per lane");
-    {
-        double tq[NLN], keep[NLN];
-        int lastb[NLN];
-        const uint32_t marks = Q.fold_marks[is_short][lane];
-        const uint8_t* l2s = line2sfb(Q, g.block_type);
-        // Terms are computed for EVERY line, evaluated band or not: a cached band's sum is never read.
-        // keep[k] = 0 at a band start, 1 elsewhere: fma(sum, keep, t) is `sum + t` or `t` with ONE rounding, i.e.
-        // exactly the reference's `noise += t` (or a fresh sum); no contraction is involved, the fma is explicit.
-        // |xr| - pow43 * step: the product of two Float32 values is exact in f64, so the explicit fma's single rounding is the
-        // reference's (a product, then a difference).
-        // !may_big (the usual case): every quantized value is below QT_N (see above), nothing to clamp; else the clamped look-up is
-        // replaced in the pass that follows
-#define NOISE_TERMS(IDX) _Pragma("unroll") for (int k = 0; k < NLN; k++) { \
-            const int j = NLN * lane + k; \
-            const int bnd = l2s[j]; \
-            const float bstep = L.bstep[bnd]; \
-            const float xa = L.xr[j]; const int iv = ix[j]; \
-            const float pw = Q.pow43[IDX]; \
-            const double x = __builtin_fma(-(double)pw, (double)bstep, d_abs((double)xa)); \
-            tq[k] = x * x; \
-            keep[k] = one_unless_bit(marks, k); \
-            lastb[k] = bnd; \
-        }
-        if (!may_big) { NOISE_TERMS(iv) } else { NOISE_TERMS(iv < QT_N ? iv : QT_N - 1) }
-#undef NOISE_TERMS
-        if (may_big) {                                   // rare: quantized values beyond the part of pow43 staged in LDS
-#pragma unroll
-            for (int k = 0; k < NLN; k++) {
-                const int j = NLN * lane + k;
-                const int iv = ix[j];
-                if (iv >= QT_N) {
-                    const double x = __builtin_fma(-(double)T.pow43[iv], (double)L.bstep[lastb[k]], d_abs((double)L.xr[j]));
-                    tq[k] = x * x;
-                }
-            }
-        }
-        PH_MARK(L, PH_N_LINES, tm_);
-        const int nsteps = (maxlen + NLN - 1) / NLN + 1;
-        double carry = 0.0;
-        for (int st = 0; st + 1 < nsteps; st++) {
-            double sacc = carry;
-#pragma unroll
-            for (int k = 0; k < NLN; k++) sacc = __builtin_fma(sacc, keep[k], tq[k]);
-            carry = wave_shr1d(sacc, 0.0);
-        }
-        {
-            double sacc = carry;
-#pragma unroll
-            for (int k = 0; k < NLN; k++) { sacc = __builtin_fma(sacc, keep[k], tq[k]); tq[k] = sacc; }   // tq := running sums of the last step
-        }
-#pragma unroll
-        for (int k = 0; k < NLN; k++) if ((marks >> (16 + k)) & 1u) L.nsum[lastb[k]] = tq[k];
-        wave_sync();
-        PH_MARK(L, PH_N_FOLD, tm_);
-    }
+    //    NLN is the table set's, or 3 for the short window: wave-uniform branches per call pick the body.  The table set's value is read from the kernel's arguments (Tables::noise_nln, a
+    //    scalar load that does not depend on the band pass above), not from its copy in QuantTabs: a branch on a value in LDS adds a third
+    //    dependent LDS round trip to the line pass, which cost most of what the two lines save (profiles/noise_lines_ab_parent_vs_result.txt).
+    if (m_fresh && hib <= T.noise_hib3[is_short]) q_noise_band_sums<3>(T, g, ix, may_big, maxlen, lane, L, Q, tm_);   // every fresh band ends at or below line 192
+    else if (T.noise_nln == 7) q_noise_band_sums<7>(T, g, ix, may_big, maxlen, lane, L, Q, tm_);
+    else q_noise_band_sums<9>(T, g, ix, may_big, maxlen, lane, L, Q, tm_);
     // 3) per band: distortion ratio x = noise / xmin (div_by_f32: the division's result from the reciprocal calc_xmin left), its class
     //    (over? tmp) -- without the logarithm wherever that is safe (noise_class, lhip_math.h) -- and the cache.  The reference caches
     //    the Float32 copy of the noise and divides it by xmin again in every later call; that quotient is formed here, once.  Lanes whose

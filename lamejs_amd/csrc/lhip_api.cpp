@@ -687,6 +687,10 @@ int64_t lhip_debug_read(int what, void* dst, size_t cap) {
         const int64_t v[2] = {(int64_t)__atomic_load_n(&round_stats().head, __ATOMIC_RELAXED), (int64_t)__atomic_load_n(&round_stats().full, __ATOMIC_RELAXED)};
         const size_t n = cap < sizeof v ? cap : sizeof v; memcpy(dst, v, n); return (int64_t)n;
     }
+    if (what == 12) {                                   // calc_noise calls so far with 7 / with 9 / with 3 lines per lane (NoiseLineStats, k_quant.h; the 64-lane simulation counts)
+        const int64_t v[3] = {(int64_t)__atomic_load_n(&noise_line_stats().n7, __ATOMIC_RELAXED), (int64_t)__atomic_load_n(&noise_line_stats().n9, __ATOMIC_RELAXED), (int64_t)__atomic_load_n(&noise_line_stats().n3, __ATOMIC_RELAXED)};
+        const size_t n = cap < sizeof v ? cap : sizeof v; memcpy(dst, v, n); return (int64_t)n;
+    }
 #endif
 #ifdef LHIP_PHASE_PROF
     if (what == 9) { const size_t n = cap < sizeof g_call_prof ? cap : sizeof g_call_prof; memcpy(dst, g_call_prof, n); return (int64_t)n; }

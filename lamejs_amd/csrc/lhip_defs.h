@@ -113,7 +113,7 @@ struct Tables {
     const int32_t *psy_fold; int psy_maxlen_l; // psyA's partition fold: [64][3] marks | partition numbers of the lane's 8 lines; longest long partition
     const int32_t *bvtab;                   // count_bits: [289] by big_values / 2: a1 | a2 << 10 | region0_count << 20 | region1_count << 24 | sfb_count1 << 27
     const void *qtabs_img;                  // the quantization kernels' LDS tables (QuantTabs, k_quant.h) as one prebuilt image: a workgroup copies it flat instead of gathering it from the source tables
-    const int32_t *fold_marks, *wpre;       // calc_noise's fold: band-start / band-end marks per lane [2][64]; widest band among bands 0 .. b [24 long | 40 short]
+    const int32_t *fold_marks, *wpre;       // calc_noise's fold: band-start / band-end marks per lane [2][64], for noise_nln lines per lane and for the short window's 3; widest band among bands 0 .. b [24 long | 40 short]
     // input gains and downmix (extension; Lame.js:1551-1584; lhip_layout.h PcmSrc).  From the blob where it has the entries, defaults otherwise;
     // at the end of the record so that nothing in front of them moves
     double scale_left, scale_right;
@@ -121,6 +121,8 @@ struct Tables {
         do_scale, do_scale_left, do_scale_right,   // the gain is in force (the reference's NEQ(g, 0) && NEQ(g, 1), resolved by tables.js)
         in_mix;                             // 0: `scale` at most / 1: per-channel gains / 2: downmix (PcmSrc::mix)
     float pcm_limit;                        // Float32 input: |x| above this is outside the contract: PCM_F32_LIMIT / max(1, |gain left|, |gain right|)
+    int noise_nln;                          // calc_noise's fold: lines per lane, 7 where 448 lines hold every evaluated band (sfb_l[21] and 3 * sfb_s[12] <= 448), else 9; fold_marks is laid out for it
+    int noise_hib3[2];                      // calc_noise's short window: the highest band that ends at or below line 192 ([0] long, [1] short blocks)
 };
 
 // Per-granule-channel side information produced by the quantization kernel and consumed by the

@@ -157,7 +157,9 @@ template <int PAIR, int SKIP> __global__ __launch_bounds__(64 * QF_WAVES, LHIP_Q
     __shared__ QuantTabs Q;
     __shared__ QuantLds L[QF_WAVES];
     __shared__ FastPair FP[QF_WAVES / 2];
+#ifndef LHIP_PHASE_PROF         // (the profiling build's QuantLds carries the phase counters: one workgroup of this kernel per CU there, and its phases are not profiled)
     static_assert(QF_WAVES * sizeof(QuantLds) + sizeof(QuantTabs) + sizeof(FP) <= 80 * 1024, "g_quant_fast: LDS budget for 2 workgroups per CU exceeded");
+#endif
     static_assert(sizeof(FP) / sizeof(int) <= 64 * QF_WAVES, "the pair records are zeroed by one store per thread");
     const QArgs* A = (const QArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     q_copy_tabs(A->T, Q, threadIdx.x, 64 * QF_WAVES);

@@ -270,9 +270,12 @@ static bool derive_index_tables(TableSet& ts, void* stream) {
         }
         memcpy(extra.data() + amp_at, amp, sizeof amp);
     }
-    // calc_noise's systolic fold (k_quant.h): lane l owns the lines 9 l .. 9 l + 8 of the (re-ordered) spectrum; per lane, bit k =
-    // line 9 l + k is the first line of its scalefactor band, bit 16 + k = it is the last one ([0..63] long, [64..127] short blocks);
-    // then the widest band among bands 0 .. b: 24 entries for long blocks, 40 for short ones (band = 3 * sfb + window)
+    // calc_noise's systolic fold (k_quant.h): lane l owns the lines n l .. n l + n - 1 of the (re-ordered) spectrum, n = noise_nln; per lane,
+    // bit k = line n l + k is the first line of its scalefactor band, bit 16 + k = it is the last one ([0..63] long, [64..127] short blocks);
+    // then the widest band among bands 0 .. b: 24 entries for long blocks, 40 for short ones (band = 3 * sfb + window).
+    // noise_nln: calc_noise reads the sums of the bands below psymax only -- 21 long or 3 * 12 short ones, sfb21_extra being refused above --
+    // so the lines from sfb_l[21] and 3 * sfb_s[12] on are never needed: 7 lines per lane (448 lines) where both borders fit, else all 576
+    // with 9.  (6 would fit 48 kHz, but an even lane stride brings LDS bank conflicts.)
     const size_t fold_at = extra.size();
     extra.resize(fold_at + 128 + 24 + 40 + 289);
     {
@@ -285,17 +288,29 @@ static bool derive_index_tables(TableSet& ts, void* stream) {
             const int st = h_ss[sfb], w = h_ss[sfb + 1] - st;
             band_s[d] = 3 * sfb + (w > 0 ? (d - 3 * st) / w : 0);
         }
+        const int nln = (h_sl[SBPSY_l] <= 64 * 7 && 3 * h_ss[SBPSY_s] <= 64 * 7) ? 7 : 9;
+        T.noise_nln = nln;
         for (int sh = 0; sh < 2; sh++) {
             const std::vector<int>& b = sh ? band_s : band_l;
             for (int ln = 0; ln < 64; ln++) {
                 uint32_t m = 0;
-                for (int kk = 0; kk < 9; kk++) {
-                    const int jj = 9 * ln + kk;
+                for (int kk = 0; kk < nln; kk++) {
+                    const int jj = nln * ln + kk;
                     if (jj == 0 || b[jj - 1] != b[jj]) m |= 1u << kk;
                     if (jj == 575 || b[jj + 1] != b[jj]) m |= 1u << (16 + kk);
                 }
+                // the short window (3 lines per lane, lines 0..191): the same marks at bits 12 + k and 28 + k (the 9-line form uses 0..8 and 16..24)
+                for (int kk = 0; kk < 3; kk++) {
+                    const int jj = 3 * ln + kk;
+                    if (jj == 0 || b[jj - 1] != b[jj]) m |= 1u << (12 + kk);
+                    if (b[jj + 1] != b[jj]) m |= 1u << (28 + kk);
+                }
                 extra[fold_at + 64 * sh + ln] = (int32_t)m;
             }
+            // the highest band that ends at or below line 192
+            int hb = -1;
+            for (int jj = 0; jj < 192; jj++) if (b[jj + 1] != b[jj]) hb = b[jj];
+            T.noise_hib3[sh] = hb;
         }
         int mx = 0;
         for (int i = 0; i < 24; i++) { if (i < SBMAX_l) { const int w = h_sl[i + 1] - h_sl[i]; if (mx < w) mx = w; } extra[fold_at + 128 + i] = mx; }
