@@ -346,6 +346,33 @@ int lhip_debug_gain_windows(int fs, int channels, const float* l, const float* r
  * 2) * nsamples elements -- interleaved, or the left plane followed by the right one.  left / right (right: two channels only) receive nsamples floats each,
  * *rejected the samples read as zero (limit 131072).  misalign must be a multiple of the element size for the 4- and 8-byte types.  Returns 0 or < 0. */
 int lhip_debug_ingest(int format, int channels, const void* bytes, size_t nsamples, size_t misalign, float* left, float* right, int64_t* rejected);
+/* Test hook.  lhip_debug_quant_probe: THE KERNEL g_quant_probe (in the simulation libraries: its body) over n records `in`, results to the n records `out`, with
+ * the tables of stream s.  The kernel calls the quantization search's own device functions -- q_ath_pseudo, q_init_outer_loop, q_init_xrpow, q_calc_xmin,
+ * q_pecalc, q_count_bits with the full and with the short round count, q_calc_noise_ -- and restates none.  It reads and writes nothing of the stream's state.
+ * One wave per workgroup; a wave takes record after record, so its LDS record serves one record after the other.  max_workgroups: 0 the default grid, 1 every
+ * record through one wave, k at most k workgroups (the simulations run at most 3 waves).  Refused (< 0, lhip_last_error says why): null arguments, n = 0 or
+ * above 2^20, a quality 7 stream (its table set never calls calc_noise), and any record with a block_type outside 0..3, a global_gain outside 0..255,
+ * scalefac_scale or preflag outside 0..1, preflag on a short block, a subblock_gain outside 0..7 (or non-zero on another block type), a scalefac outside 0..255,
+ * a band step outside the pow20 table (-116 .. 257) in one of the scalefactor states below, an ix_in outside 0..8206, an unknown flag, or an xr, ratio or
+ * ath_adjust that is not finite (ratio >= 0, ath_adjust > 0).  Little-endian, natural alignment, no padding but the named fields.
+ * Record in, 4144 bytes:   f32 xr[576] (natural order, as lhip_debug_read(0) gives it; the probe applies the analog-silence rule) | f32 ratio[122] (the E layout
+ *   of lhip_debug_read(2)) | f64 ath_adjust | i32 block_type, global_gain, scalefac_scale, preflag, subblock_gain[3], scalefac[39], flags (bit 0: ix_in is
+ *   given), pad | i16 ix_in[576] (magnitudes, quantizer line order).
+ * Record out, 6352 bytes (zero where a step did not run or does not write):   f64 xrpow_max, pe | i32 active, max_nonzero_coeff, tail0, pad | f32 xr[576] (after
+ *   the silence rule, quantizer line order) | f32 xmin[40] | 2 evaluations | 8 calc_noise calls.
+ *   An evaluation, 1192 bytes:  i32 bits, big_values, count1, count1table_select, table_select[3], region0_count, region1_count, ran | i16 ix[576].
+ *   A calc_noise call, 184 bytes:  f64 max_noise | i32 over_count, over_SSD, ran, pad | f32 distort[40].
+ * Steps.  1: q_init_outer_loop, q_init_xrpow -> active, xrpow_max, xr; an inactive record ends here.  2: q_calc_xmin (want_tail0) -> xmin, max_nonzero_coeff,
+ * tail0; q_pecalc of ratio with the block type's masking_lower -> pe.  3: one evaluation at global_gain with all scalefactors zero and no noise cache (the bin
+ * search's state): q_count_bits with the full round count -> evaluation 0; where tail0 is set, also with the short round count -> evaluation 1, after the
+ * words 256..287 of the wave's working spectrum were filled with a pattern and zeroed as the search's caller zeroes them.  A refused gain (bits = 100000)
+ * writes bits and ran only.  4: calc_noise with the record's global_gain, scalefac_scale, preflag, subblock_gain and scalefac on ix_in (flag) or on the lines
+ * of step 3 (all zero where the gain was refused) -- a: no cache, max_noise wanted; b: no cache, not wanted; c: fills an empty cache, not wanted; d: the same
+ * again (every band cached), wanted; e: scalefac[0] ^= 1 (band 0 alone is fresh), not wanted; f: then scalefac[sfb] ^= 1 for every sfb % 3 == 0 below psymax,
+ * wanted; g: then scalefac[b] ^= 1 for b the highest band that ends at or below line 192 (it alone is fresh: the border of the 3-line body), not wanted; h: then
+ * scalefac[b + 1] ^= 1 (the band above alone), wanted.  c-h run only where lines exist (ix_in given, or the gain not refused).  max_noise is 0 where calc_noise did not form it (not wanted and
+ * over_count > 0).  Returns 0 or < 0. */
+int lhip_debug_quant_probe(lhip_stream* s, const void* in, size_t n, void* out, int max_workgroups);
 
 /* Debug/test taps (tests only): copy intermediate results of the most recent batch to the host.
  * what: 0 xr [granule][ch][576] f32, 1 blocktype [granule][ch] i32, 2 E [granule][psy ch][122] f32 (psy ch = ch, or L R mid side in joint stereo; thresholds

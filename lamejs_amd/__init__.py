@@ -125,9 +125,12 @@ ABI = {
     "lhip_replay_gain": (_int, [_ptr, _pi32, _pi64, _pi64]),
     "lhip_debug_gain_histogram": (_int, [_ptr, _ptr]),
     "lhip_debug_gain_windows": (_int, [_int, _int, _ptr, _ptr, _size, _ptr, _ptr]),
+    "lhip_debug_quant_probe": (_int, [_ptr, _ptr, _size, _ptr, _int]),
     "lhip_last_error": (ctypes.c_char_p, []),
     "lhip_version": (ctypes.c_char_p, []),
 }
+
+TEST_HOOKS_OPTIONAL_IN_NAMED_LIBRARIES = frozenset({"lhip_debug_quant_probe"})      # see load_library
 
 _lib = None
 
@@ -143,6 +146,10 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
                         "lamejs_amd has no CPU fallback.")
     lib = ctypes.CDLL(str(p))
     for name, (restype, argtypes) in ABI.items():      # a library without one of these entries is not this package's library
+        # ... but for a test hook in a library named by the caller (a simulation, a variant build): one built from a tree that did not have the hook yet
+        # still serves every caller that does not use it, and a use of the hook fails loudly (AttributeError).  The product library has them all.
+        if path is not None and name in TEST_HOOKS_OPTIONAL_IN_NAMED_LIBRARIES and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if path is None:

@@ -17,6 +17,7 @@
 #include "k_quant_tail.h"      // how a launch of the persistent quantization kernel ends (the one-lane simulation has no workgroups: it runs kb_quant)
 #endif
 #include "k_quant_fast.h"      // the speculative pass of a fast table set (quality 7): the bin search alone
+#include "k_quant_probe.h"     // test hook: the search's pure functions over caller-supplied records (lhip_debug_quant_probe)
 #include "k_bits.h"
 #include "k_crc.h"
 #include "k_ingest.h"
@@ -45,6 +46,7 @@ using namespace lhip;
 #include "k_state.h"
 #include "k_frame.h"
 #ifndef LHIP_HOSTSIM
+#include <dlfcn.h>             // lhip_debug_quant_probe finds its kernel's code object beside the library
 #include "lhip_kernels.h"
 #endif
 #include "lhip_gain.h"
@@ -915,6 +917,74 @@ int lhip_debug_gain_windows(int fs, int channels, const float* l, const float* r
     } else if (g) set_err("hipMalloc failed");
     rt::dfree(src); rt::dfree(dB); rt::dfree(dE); rt::dfree(dIO); rt::dfree(dSD); rt::dfree(dGD); rt::dfree(rows);
     return ok ? (int)nwin : LHIP_ERR_INTERNAL;
+}
+// Test hook.  lhip_debug_quant_probe: the kernel g_quant_probe (in the simulations: its body, k_quant_probe.h) over n caller-supplied records with the tables of
+// stream s.  Every index the kernel forms from a record is checked here first: the block type, the gain, the step of every band in each of the scalefactor
+// states the probe visits (the pow20 table), the quantized lines (pow43), and that the numbers are finite (a NaN line has no quantized value).
+static const char* probe_check_record(const ProbeIn& I, const int32_t* pretab) {
+    if (I.block_type < 0 || I.block_type > 3) return "block_type outside 0..3";
+    if (I.global_gain < 0 || I.global_gain > 255) return "global_gain outside 0..255";
+    if ((I.scalefac_scale | 1) != 1 || (I.preflag | 1) != 1) return "scalefac_scale / preflag outside 0..1";
+    const bool sh = I.block_type == SHORT_TYPE;
+    if (sh && I.preflag) return "preflag on a short block (pretab has long bands only)";
+    for (int w = 0; w < 3; w++) if (I.subblock_gain[w] < 0 || I.subblock_gain[w] > 7 || (!sh && I.subblock_gain[w])) return "subblock_gain outside 0..7 (0 unless the block is short)";
+    if (!(I.ath_adjust > 0.0) || !(I.ath_adjust < 1e30)) return "ath_adjust not positive and finite";
+    for (int i = 0; i < 576; i++) if (!(std::fabs((double)I.xr[i]) < 1e30)) return "xr not finite";
+    for (int i = 0; i < E_STRIDE; i++) if (!(I.ratio[i] >= 0.f) || !(I.ratio[i] < 3e38f)) return "ratio negative or not finite";
+    const int psymax = sh ? 3 * SBPSY_s : SBPSY_l;
+    for (int sfb = 0; sfb < SFBMAX; sfb++) if (I.scalefac[sfb] < 0 || I.scalefac[sfb] > 255) return "scalefac outside 0..255";
+    for (int sfb = 0; sfb < psymax; sfb++) {
+        // the states of calls a-d, e and f: the scalefactor as given, and with its lowest bit flipped
+        for (int flip = 0; flip < 2; flip++) {
+            const int sf = I.scalefac[sfb] ^ flip;
+            const int st = I.global_gain - ((sf + (I.preflag ? pretab[sfb] : 0)) << (I.scalefac_scale + 1)) - (sh ? I.subblock_gain[sfb % 3] : 0) * 8;
+            if (st < -Q_MAX2 || st > Q_MAX) return "a band's step outside the pow20 table";
+        }
+    }
+    if (I.flags & ~1) return "unknown flag";
+    if (I.flags & 1) for (int i = 0; i < 576; i++) if (I.ix_in[i] < 0 || I.ix_in[i] > IXMAX_VAL) return "ix_in outside 0..IXMAX_VAL";
+    return nullptr;
+}
+int lhip_debug_quant_probe(lhip_stream* s, const void* in, size_t n, void* out, int max_workgroups) {
+    if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    if (!in || !out || n == 0 || n > (size_t)1 << 20 || max_workgroups < 0) { set_err("lhip_debug_quant_probe: bad argument"); return LHIP_ERR_INTERNAL; }
+    if (s->ts->fast) { set_err("lhip_debug_quant_probe: a quality 7 stream (its table set never calls calc_noise)"); return LHIP_ERR_INTERNAL; }
+    const lhtb_entry* pt = find_entry(s->ts->blob.data(), "pretab");
+    if (!pt || pt->dtype != 1 || pt->count < (uint32_t)SBMAX_l) { set_err("lhip_debug_quant_probe: tables blob without pretab"); return LHIP_ERR_INTERNAL; }
+    const int32_t* pretab = (const int32_t*)(s->ts->blob.data() + pt->offset);
+    const ProbeIn* rec = (const ProbeIn*)in;
+    for (size_t i = 0; i < n; i++) {
+        ProbeIn I; memcpy(&I, rec + i, sizeof I);       // (the caller's buffer need not be aligned)
+        if (const char* why = probe_check_record(I, pretab)) { set_err("lhip_debug_quant_probe: record " + std::to_string(i) + ": " + why); return LHIP_ERR_INTERNAL; }
+    }
+    Context* ctx = s->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!rt::set_device(ctx->device)) return LHIP_ERR_INTERNAL;
+    void* st = ctx->stream;
+    ProbeIn* dIn = (ProbeIn*)rt::dmalloc(n * sizeof(ProbeIn));
+    ProbeOut* dOut = (ProbeOut*)rt::dmalloc(n * sizeof(ProbeOut));
+    bool ok = dIn && dOut;
+    if (ok) {
+        ok = rt::h2d(dIn, in, n * sizeof(ProbeIn), st) && rt::dzero(dOut, n * sizeof(ProbeOut), st);
+        const int nn = (int)n;
+#ifndef LHIP_HOSTSIM
+        if (ok) {
+            const int grid = max_workgroups > 0 ? (nn < max_workgroups ? nn : max_workgroups) : (nn < 1024 ? nn : 1024);
+            ProbeArgs a; a.T = s->ts->T; a.pb = s->ts->pb10; a.in = dIn; a.out = dOut; a.n = nn; a.grid = grid;
+            const std::string e = probe_launch(rt::phys(ctx->device), a, st);
+            if (!e.empty()) { set_err("g_quant_probe: " + e); ok = false; }
+        }
+#else
+        if (ok) {
+            ok = rt::sync(st);
+            const int cap = max_workgroups > 0 && max_workgroups < PROBE_SIM_WAVES ? max_workgroups : PROBE_SIM_WAVES;
+            if (ok) quant_probe_sim_run(s->ts->T, s->ts->pb10, dIn, dOut, nn, nn < cap ? nn : cap);
+        }
+#endif
+        ok = ok && rt::d2h(out, dOut, n * sizeof(ProbeOut), st) && rt::sync(st);
+    } else set_err("hipMalloc failed");
+    rt::dfree(dIn); rt::dfree(dOut);
+    return ok ? 0 : LHIP_ERR_INTERNAL;
 }
 int lhip_debug_info_toc(const int64_t* frames, size_t ncalls, int kbps, uint8_t* toc) {
     if ((!frames && ncalls) || !toc || kbps <= 0) { set_err("lhip_debug_info_toc: bad argument"); return LHIP_ERR_INTERNAL; }

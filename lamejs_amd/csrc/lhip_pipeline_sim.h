@@ -25,6 +25,14 @@ static void gain_sim_run(const Tables& T, const Workspace& W, const StreamDesc* 
         if (D[s].channels == 2) WAVE_RUN(kb_gain<2>(D, s, b - D[s].wave0, lane_, LG)); else WAVE_RUN(kb_gain<1>(D, s, b - D[s].wave0, lane_, LG));
     }
 }
+// g_quant_probe (lhip_debug_quant_probe; k_quant_probe.h): `grid` waves, each with an LDS record of its own that serves its records one after the other
+enum { PROBE_SIM_WAVES = 3 };
+static void quant_probe_sim_run(const Tables& T, const PowBase& pb, const ProbeIn* in, ProbeOut* out, int n, int grid) {
+    static thread_local QuantLds LP[PROBE_SIM_WAVES]; static thread_local QuantTabs QT;
+    q_load_tabs(T, QT, 0, 1);
+    for (int b = 0; b < grid; b++)
+        for (int r = b; r < n; r += grid) WAVE_RUN(kb_quant_probe(T, pb, in, out, r, lane_, LP[b], QT));
+}
 static inline bool g_kt_on_() { return false; }
 static bool collect_kernel_times(void*) { return true; }
 static bool collect_repair_stats(Context*, BatchPlan&, bool, const int32_t*) { return true; }      // (run_pipeline counted them itself)

@@ -21,6 +21,8 @@ int lo_frame_bytes_max(const lo_enc* e);
 void lo_enable_tap(lo_enc* e);
 const void* lo_get_tap(const lo_enc* e);
 size_t lo_tap_size(void);
+/* the quantization probe (lo_quant.c): n records of 4144 bytes in, n of 6352 bytes out, with e's tables; e's stream state is left as it was */
+void lo_quant_probe(lo_enc* e, const void* in, size_t n, void* out);
 #ifdef __cplusplus
 }
 #endif

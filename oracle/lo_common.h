@@ -149,6 +149,10 @@ typedef struct lo_tap {
     int global_gain[2][2], part2_3_length[2][2], part2_length[2][2];
     int mode_ext;                  /* joint stereo: the frame's M/S decision */
     double pe[2][2], pe_MS[2][2], ms_ener_ratio[2];
+    /* the search's final state per granule and channel (after outer_loop, before the scalefactors are stored): what calc_noise last kept */
+    int active[2][2];              /* init_xrpow found energy; 0: the fields below are zero */
+    int scalefac[2][2][SFBMAX], scalefac_scale[2][2], preflag[2][2], subblock_gain[2][2][3];
+    int l3_enc[2][2][576];         /* magnitudes, quantizer line order */
 } lo_tap;
 
 #endif

@@ -1050,6 +1050,19 @@ static double lo_on_pe_resv(lo_enc* e, double pe[2][2], int32_t targ_bits[2], do
     return max_bits;
 }
 
+/* tap: the search's final state of a granule-channel (lo_tap) */
+static void lo_tap_search(lo_enc* e, int gr, int ch, const lo_gr* gi, int active) {
+    lo_tap* t = e->tap;
+    int i;
+    if (!t) return;
+    t->active[gr][ch] = active;
+    for (i = 0; i < SFBMAX; i++) t->scalefac[gr][ch][i] = active ? gi->scalefac[i] : 0;
+    t->scalefac_scale[gr][ch] = active ? gi->scalefac_scale : 0;
+    t->preflag[gr][ch] = active ? gi->preflag : 0;
+    for (i = 0; i < 3; i++) t->subblock_gain[gr][ch][i] = active ? gi->subblock_gain[i] : 0;
+    for (i = 0; i < 576; i++) t->l3_enc[gr][ch][i] = active ? gi->l3_enc[i] : 0;
+}
+
 /* CBRNewIterationLoop.js:25-90 with the reservoir in use: ResvFrameBegin (Reservoir.js:130-180), on_pe per granule, ResvAdjust per
  * granule-channel, ResvFrameEnd (Reservoir.js:243-293).  The frame's bits then go through the continuous stream writer. */
 static void lo_iteration_loop_resv(lo_enc* e, double pe[2][2], lo_ratio ratio[2][2], const double ms_ener_ratio[2]) {
@@ -1086,7 +1099,8 @@ static void lo_iteration_loop_resv(lo_enc* e, double pe[2][2], lo_ratio ratio[2]
                 lo_calc_xmin(e, &ratio[gr][ch], gi, l3_xmin);
                 if (e->tap) memcpy(e->tap->l3_xmin[gr][ch], l3_xmin, sizeof l3_xmin);
                 lo_outer_loop(e, gi, l3_xmin, xrpow, ch, targ_bits[ch]);
-            }
+                lo_tap_search(e, gr, ch, gi, 1);
+            } else lo_tap_search(e, gr, ch, gi, 0);
             lo_best_scalefac_store(e, gr, ch);
             if (c->use_best_huffman == 1) lo_best_huffman_divide(c, gi);
             e->ResvSize -= gi->part2_3_length + gi->part2_length;                       /* ResvAdjust */
@@ -1161,7 +1175,8 @@ static void lo_iteration_loop(lo_enc* e, lo_ratio ratio[2][2], const double ms_e
                 lo_calc_xmin(e, &ratio[gr][ch], gi, l3_xmin);
                 if (e->tap) memcpy(e->tap->l3_xmin[gr][ch], l3_xmin, sizeof l3_xmin);
                 lo_outer_loop(e, gi, l3_xmin, xrpow, ch, targ_bits[ch]);
-            }
+                lo_tap_search(e, gr, ch, gi, 1);
+            } else lo_tap_search(e, gr, ch, gi, 0);
             /* iteration_finish_one */
             lo_best_scalefac_store(e, gr, ch);
             if (c->use_best_huffman == 1) lo_best_huffman_divide(c, gi);
@@ -1177,4 +1192,106 @@ static void lo_iteration_loop(lo_enc* e, lo_ratio ratio[2][2], const double ms_e
     e->ResvSize += mean_bits * c->mode_gr;
     e->resvDrain_post = e->ResvSize;
     e->ResvSize = 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* the quantization probe (tests/quant_probe_cases.py)                  */
+/* ------------------------------------------------------------------ */
+/* What the library's lhip_debug_quant_probe computes from a record, from the functions above alone -- serial, one form: init_outer_loop, init_xrpow,
+ * calc_xmin, pecalc, count_bits at the record's gain with zero scalefactors, and calc_noise eight times on the record's scalefactor state (a, b without a
+ * cache; c-h with one that starts zeroed; e and f after flipping the lowest bit of scalefac[0] / of every third scalefactor; g and h after flipping that of
+ * the highest band that ends at or below line 192 / of the band above it).  The records are the
+ * library's (include/lamejs_hip.h in the product tree states them); the structs below restate the layout. */
+typedef struct {
+    float xr[576]; float ratio[122]; double ath_adjust;
+    int32_t block_type, global_gain, scalefac_scale, preflag, subblock_gain[3], scalefac[SFBMAX], flags, pad_;
+    int16_t ix_in[576];
+} lo_probe_in;
+typedef struct { int32_t bits, big_values, count1, count1table_select, table_select[3], region0_count, region1_count, ran; int16_t ix[576]; } lo_probe_eval;
+typedef struct { double max_noise; int32_t over_count, over_SSD, ran, pad_; float distort[SFBMAX + 1]; } lo_probe_noise;
+typedef struct {
+    double xrpow_max, pe;
+    int32_t active, max_nonzero_coeff, tail0, pad_;
+    float xr[576], xmin[SFBMAX + 1];
+    lo_probe_eval ev[2];
+    lo_probe_noise nz[8];
+} lo_probe_out;
+_Static_assert(sizeof(lo_probe_in) == 4144 && sizeof(lo_probe_out) == 6352 && sizeof(lo_ratio) == 122 * 4, "probe record layouts");
+
+void lo_quant_probe(lo_enc* e, const void* in, size_t n, void* out) {
+    const lo_cfg* c = &e->c;
+    const double keep_ath = e->ATH_adjust, keep_ml = e->masking_lower;
+    static lo_gr g0, w;               /* the oracle is single-threaded */
+    size_t r;
+    for (r = 0; r < n; r++) {
+        lo_probe_in I;
+        lo_probe_out O;
+        lo_ratio ratio;
+        float xrpow[576], l3_xmin[SFBMAX], distort[SFBMAX];
+        lo_noise_data prev;
+        int i, k, bits, lines, b3, ncalls;
+        memcpy(&I, (const char*)in + r * sizeof I, sizeof I);
+        memset(&O, 0, sizeof O);
+        memcpy(&ratio, I.ratio, sizeof ratio);
+        memset(&g0, 0, sizeof g0);
+        memset(l3_xmin, 0, sizeof l3_xmin);
+        e->ATH_adjust = I.ath_adjust;
+        g0.block_type = I.block_type;
+        memcpy(g0.xr, I.xr, sizeof g0.xr);
+        e->masking_lower = (g0.block_type != SHORT_TYPE) ? c->masking_lower_long : c->masking_lower_short;
+        /* 1 */
+        lo_init_outer_loop(e, &g0);
+        O.active = lo_init_xrpow(&g0, xrpow);
+        O.xrpow_max = g0.xrpow_max;
+        memcpy(O.xr, g0.xr, sizeof O.xr);
+        if (O.active) {
+            /* 2 */
+            lo_calc_xmin(e, &ratio, &g0, l3_xmin);
+            for (i = 0; i < g0.psymax; i++) O.xmin[i] = l3_xmin[i];
+            O.max_nonzero_coeff = g0.max_nonzero_coeff;
+            O.tail0 = 1;
+            for (i = 512; i < 576; i++) if (!(D(g0.xr[i]) == 0)) O.tail0 = 0;
+            O.pe = (g0.block_type == SHORT_TYPE) ? lo_pecalc_s(&ratio, e->masking_lower) : lo_pecalc_l(&ratio, e->masking_lower);
+            /* 3 */
+            w = g0;
+            w.global_gain = I.global_gain;
+            bits = lo_count_bits(c, xrpow, &w, NULL);
+            O.ev[0].bits = bits; O.ev[0].ran = 1;
+            if (bits != LARGE_BITS) {
+                O.ev[0].big_values = w.big_values; O.ev[0].count1 = w.count1; O.ev[0].count1table_select = w.count1table_select;
+                for (i = 0; i < 3; i++) O.ev[0].table_select[i] = w.table_select[i];
+                O.ev[0].region0_count = w.region0_count; O.ev[0].region1_count = w.region1_count;
+                for (i = 0; i < 576; i++) O.ev[0].ix[i] = (int16_t)w.l3_enc[i];
+            }
+            if (O.tail0) O.ev[1] = O.ev[0];          /* one form: the library's short round count must give the same */
+            /* 4 */
+            lines = bits != LARGE_BITS;
+            if (I.flags & 1) { for (i = 0; i < 576; i++) w.l3_enc[i] = I.ix_in[i]; lines = 1; }
+            else if (!lines) memset(w.l3_enc, 0, sizeof w.l3_enc);
+            w.table_select[0] = w.table_select[1] = w.table_select[2] = 0;
+            (void)lo_noquant_count_bits(c, &w, NULL);      /* big_values and count1 of these lines: calc_noise_core's three forms */
+            w.scalefac_scale = I.scalefac_scale; w.preflag = I.preflag;
+            for (i = 0; i < 3; i++) w.subblock_gain[i] = I.subblock_gain[i];
+            for (i = 0; i < SFBMAX; i++) w.scalefac[i] = I.scalefac[i];
+            memset(&prev, 0, sizeof prev);
+            /* g, h: the highest band that ends at or below line 192 alone fresh, then the band above it alone */
+            b3 = -1;
+            for (i = 0, k = 0; i < w.psymax && k + w.width[i] <= 192; k += w.width[i], i++) b3 = i;
+            ncalls = !lines ? 2 : (b3 >= 0 && b3 + 1 < w.psymax) ? 8 : 6;
+            for (k = 0; k < ncalls; k++) {
+                lo_noise_res res;
+                memset(&res, 0, sizeof res);
+                memset(distort, 0, sizeof distort);
+                if (k == 4) w.scalefac[0] ^= 1;
+                if (k == 5) for (i = 0; i < w.psymax; i += 3) w.scalefac[i] ^= 1;
+                if (k >= 6) w.scalefac[b3 + (k - 6)] ^= 1;
+                lo_calc_noise(c, &w, l3_xmin, distort, &res, k >= 2 ? &prev : NULL);
+                O.nz[k].max_noise = res.max_noise; O.nz[k].over_count = res.over_count; O.nz[k].over_SSD = res.over_SSD; O.nz[k].ran = 1;
+                for (i = 0; i < w.psymax; i++) O.nz[k].distort[i] = distort[i];
+            }
+        }
+        memcpy((char*)out + r * sizeof O, &O, sizeof O);
+    }
+    e->ATH_adjust = keep_ath;
+    e->masking_lower = keep_ml;
 }

@@ -39,7 +39,7 @@ def _load():
         vp, sz = ctypes.c_void_p, ctypes.c_size_t
         for name, restype, argtypes in (("lo_create", vp, [vp, sz]), ("lo_destroy", None, [vp]), ("lo_encode", ctypes.c_long, [vp, vp, vp, sz, vp, sz]),
                                         ("lo_flush", ctypes.c_long, [vp, vp, sz]), ("lo_enable_tap", None, [vp]), ("lo_get_tap", vp, [vp]),
-                                        ("lo_tap_size", sz, []), ("lo_math", None, [ctypes.c_int, vp, vp, sz])):
+                                        ("lo_tap_size", sz, []), ("lo_math", None, [ctypes.c_int, vp, vp, sz]), ("lo_quant_probe", None, [vp, vp, sz, vp])):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -82,6 +82,13 @@ class OracleStream:
     def tap(self) -> bytes:
         """The lo_tap record of the frame the last call completed (tests/stage_taps.py: TAP)."""
         return ctypes.string_at(self._lib.lo_get_tap(self._h), self._lib.lo_tap_size())
+
+    def quant_probe(self, records, out_dtype):
+        """lo_quant_probe over an array of probe records (tests/quant_probe_cases.py: REC_IN) -> array of ``out_dtype`` (REC_OUT)."""
+        rec = np.ascontiguousarray(records)
+        out = np.zeros(len(rec), dtype=out_dtype)
+        self._lib.lo_quant_probe(self._h, rec.ctypes.data, len(rec), out.ctypes.data)
+        return out
 
     def close(self):
         if self._h:
