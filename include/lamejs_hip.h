@@ -376,7 +376,10 @@ int lhip_debug_quant_probe(lhip_stream* s, const void* in, size_t n, void* out, 
 
 /* Debug/test taps (tests only): copy intermediate results of the most recent batch to the host.
  * what: 0 xr [granule][ch][576] f32, 1 blocktype [granule][ch] i32, 2 E [granule][psy ch][122] f32 (psy ch = ch, or L R mid side in joint stereo; thresholds
- * handed to the quantizer for that granule), 3 ath_adjust [frame] f64, 4 side records (struct GrSide); simulation libraries only: 10 two i64, the
+ * handed to the quantizer for that granule: en.l 22, en.s 39, thm.l 22, thm.s 39.  In a lazy batch -- no bit reservoir, on the separate kernels, at least
+ * LAMEJS_PSY_LAZY_MIN_FRAMES frame slots (a test hook read per batch; unset: 6 x the device's CUs, never below 1024; 0: always, a huge value: never) -- the
+ * en.s / thm.s entries of a psy call are computed only where they are read (a channel of the next granule slot is a short block, or the call is its stream's
+ * last of the batch and goes into the stream state) and read zero elsewhere; every smaller batch holds all 122 entries of every call), 3 ath_adjust [frame] f64, 4 side records (struct GrSide); simulation libraries only: 10 two i64, the
  * evaluations of the quantization search this process has made without / with the last round of pairs (lines 512..575 all zero / not); 12 three i64, the calc_noise calls this process has made with 7 / with 9 / with 3
  * spectrum lines per lane (counted by the 64-lane simulation; the one-lane simulation reports zeros).
  * 11 (every library; needs no batch to have run): eight i32, the speculative quantization launch of the calling thread's most recent batch -- [0] workgroups

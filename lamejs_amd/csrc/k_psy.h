@@ -163,6 +163,24 @@ template <int K> LHIP_DEV int guarded_f32_of_sum(const double (&p)[K], double sc
 #endif
 }
 
+// Who reads the short-block side of the psy call in granule slot `gslot` (both wave-uniform; W.blocktype must be final: behind g_scan_blocktype).
+// Its short thresholds (E_EN_S / E_THM_S of W.E[gslot]) are read by the quantization of slot gslot + 1 -- q_calc_xmin for a SHORT_TYPE granule, q_frame_pe
+// for L / R of that type and for mid / side when either channel has it -- and, for the stream's last call of the batch, by a later batch through the stream
+// state (kb_save): psy_need_s.  Taking the OR over the channels also covers the inter-channel masking and the mid / side thresholds, which mix the channels.
+// Its short spectra up to ecb_s are read by its own short limiting and by the next call's (the two previous sub-blocks): psy_need_f.
+// Neither holds with the bit reservoir, whose short pre-echo control reads the previous call's thresholds whatever the block type.
+LHIP_DEV int psy_need_s(const Tables& T, const Workspace& W, const StreamDesc& sd, int gslot) {
+    if (gslot >= sd.gslot0 + T.mode_gr * sd.nframes) return 1;
+    const int C = T.channels_out;
+    int s = 0;
+    for (int ch = 0; ch < C; ch++) s |= W.blocktype[(int64_t)(gslot + 1) * C + ch] == SHORT_TYPE;
+    return uni(s);
+}
+LHIP_DEV int psy_need_f(const Tables& T, const Workspace& W, const StreamDesc& sd, int gslot) {
+    if (psy_need_s(T, W, sd, gslot)) return 1;
+    return psy_need_s(T, W, sd, gslot + 1);             // (not the last slot of its stream, or the line above had returned)
+}
+
 // kb_psyA's staging of a window that lies wholly in the call's new samples, per sample format (F32: Float32 / Int16; UNIT: stride 1 known
 // at compile time -- <0, 1, 0> is the Int16 planar loop as it always was) and per input treatment (MIX: PcmSrc::mix -- 1 the channel's own gain
 // follows `scale`, 2 downmix).  The downmix instance is unrolled by hand: the trip count (16) is known, and left as one load per source and
@@ -211,8 +229,12 @@ LHIP_DEV void psya_stage_new(const PcmSrc& P, int first, int lane, float* fz) {
 // (they need the samples and nothing else, and nothing below needs them), 2 = everything else; 0 = all of it on one wave (the batched kernel);
 // 3 = everything else up to the loudness (what the scans and the search of the frame's first granule need), 4 = the rest -- partition energies, tonality,
 // short spreading: psyB's inputs -- later, on the same wave and the same LDS record (nothing but LDS carries over).
-template <int PART = 0>
+// LAZY = 1 (batches that run part 1, the scans and then part 2 as launches of their own: the block types are final when part 2 starts): the short-block
+// side -- short windowing and transforms, short energies, partitions and spreading, ecb_s / eb_s -- only where psy_need_f says somebody reads it; the
+// branches are scalar (the verdict is wave-uniform).  Peaks, loudness and every long-block value do not depend on it.
+template <int PART = 0, int LAZY = 0>
 LHIP_DEV void kb_psyA(const Tables& T, const Workspace& W, const StreamDesc* SD, const StreamIO* IO, int gslot, int ch, int lane, PsyALds& L) {
+    static_assert(LAZY == 0 || PART == 2, "the lazy form reads the block types: it exists for part 2 behind the scans only");
     const int C = T.channels_out, Cp = T.psy_channels;
     const int st = W.gslot_stream[gslot];
     const StreamDesc sd = SD[st];
@@ -247,6 +269,7 @@ LHIP_DEV void kb_psyA(const Tables& T, const Workspace& W, const StreamDesc* SD,
     PSY_DECL();
     PSY_STAMP(0);
 
+    const bool shortw = LAZY ? psy_need_f(T, W, sd, gslot) != 0 : true;      // the short spectra of this call are read (always, in the eager form)
     if (PART == 4) goto psya_tail;
     // --- fs/4 high-pass, 9 sub-block peaks (PsyModel.js:1051-1069, 1122-1132) ---
     if (PART == 0 || PART == 1) {
@@ -311,7 +334,8 @@ LHIP_DEV void kb_psyA(const Tables& T, const Workspace& W, const StreamDesc* SD,
     if (ch >= 2) {
         // mid / side spectra from the L / R ones (compute_ffts, PsyModel.js:258-273): (l + r) * SQRT2 * 0.5, rounded to f32
         const float* fl = W.fht + (int64_t)gslot * 2 * FHT_STRIDE;
-        for (int i = lane; i < FHT_STRIDE; i += LHIP_NL) {
+        const int nfht = shortw ? FHT_STRIDE : BLKSIZE;
+        for (int i = lane; i < nfht; i += LHIP_NL) {
             const double l = fl[i], r = fl[FHT_STRIDE + i];
             const float v = (ch == 2) ? (float)((l + r) * LHIP_SQRT2 * 0.5) : (float)((l - r) * LHIP_SQRT2 * 0.5);
             if (i < BLKSIZE) L.fz[fzp(i)] = v; else (&L.fs[0][0])[fzp(i - BLKSIZE)] = v;
@@ -319,7 +343,7 @@ LHIP_DEV void kb_psyA(const Tables& T, const Workspace& W, const StreamDesc* SD,
         wave_sync();
     } else {
     // --- windowing + first radix-4 stage (FFT.js:185-221 long, 140-180 short) ---
-    for (int it = lane; it < 3 * (BLKSIZE_s / 8); it += LHIP_NL) {
+    if (shortw) for (int it = lane; it < 3 * (BLKSIZE_s / 8); it += LHIP_NL) {
         const int b = it / (BLKSIZE_s / 8), j = it - b * (BLKSIZE_s / 8);
         const int k = (576 / 3) * (b + 1);
         const int i = T.fft_rv_tbl[j << 2] & 0xff;
@@ -388,14 +412,15 @@ LHIP_DEV void kb_psyA(const Tables& T, const Workspace& W, const StreamDesc* SD,
 #pragma unroll
         for (int k1 = 4, kx = 2; k1 < BLKSIZE; k1 <<= 2, kx <<= 2) {
             fht_pass(L.fz, BLKSIZE, k1, kx, lane, LHIP_NL, 0, T.fht_twiddle + 4 * off);
-            if (k1 < BLKSIZE_s) fht_pass_blocks(&L.fs[0][0], 3, BLKSIZE_s, k1, kx, lane, LHIP_NL, T.fht_twiddle + 4 * off);
+            if (k1 < BLKSIZE_s && shortw) fht_pass_blocks(&L.fs[0][0], 3, BLKSIZE_s, k1, kx, lane, LHIP_NL, T.fht_twiddle + 4 * off);
             wave_sync();
             off += kx - 1;
         }
     }
     if (Cp == 4) {                                    // joint stereo: the spectra the mid / side waves combine
         float* fo = W.fht + ((int64_t)gslot * 2 + ch) * FHT_STRIDE;
-        for (int i = lane; i < FHT_STRIDE; i += LHIP_NL) fo[i] = (i < BLKSIZE) ? L.fz[fzp(i)] : (&L.fs[0][0])[fzp(i - BLKSIZE)];
+        const int nfht = shortw ? FHT_STRIDE : BLKSIZE;          // (the mid / side waves of the slot reach the same verdict and read no further)
+        for (int i = lane; i < nfht; i += LHIP_NL) fo[i] = (i < BLKSIZE) ? L.fz[fzp(i)] : (&L.fs[0][0])[fzp(i - BLKSIZE)];
     }
     }   // ch < 2
 
@@ -412,9 +437,11 @@ LHIP_DEV void kb_psyA(const Tables& T, const Workspace& W, const StreamDesc* SD,
             else if (j <= BLKSIZE / 2) { const double re = L.fz[fzp(j)], im = L.fz[fzp(BLKSIZE - j)]; el[u] = (float)((re * re + im * im) * 0.5); }
         }
 #pragma unroll
+        for (int u = 0; u < KS; u++) es[u] = 0.f;
+        if (shortw) {
+#pragma unroll
         for (int u = 0; u < KS; u++) {
             const int it = lane + LHIP_NL * u;
-            es[u] = 0.f;
             if (it < 3 * (BLKSIZE_s / 2 + 1)) {
                 const int b = it / (BLKSIZE_s / 2 + 1), j = it - b * (BLKSIZE_s / 2 + 1);
                 const float* fsf = &L.fs[0][0];
@@ -422,13 +449,16 @@ LHIP_DEV void kb_psyA(const Tables& T, const Workspace& W, const StreamDesc* SD,
                 else { const double re = fsf[fzp(b * BLKSIZE_s + j)], im = fsf[fzp(b * BLKSIZE_s + BLKSIZE_s - j)]; es[u] = (float)((re * re + im * im) * 0.5); }
             }
         }
+        }
         wave_sync();                                  // every lane has read its operands before anything is overwritten
 #pragma unroll
         for (int u = 0; u < KE; u++) { const int j = lane + LHIP_NL * u; if (j <= BLKSIZE / 2) PSYA_FE(L)[j] = el[u]; }
+        if (shortw) {
 #pragma unroll
         for (int u = 0; u < KS; u++) {
             const int it = lane + LHIP_NL * u;
             if (it < 3 * (BLKSIZE_s / 2 + 1)) { const int b = it / (BLKSIZE_s / 2 + 1), j = it - b * (BLKSIZE_s / 2 + 1); PSYA_FES(L, b)[j] = es[u]; }
+        }
         }
     }
     wave_sync();
@@ -538,7 +568,7 @@ psya_tail:
     }
 #endif
     // --- short partitions: energy per sub-block (compute_masking_s first loop, 740-750) ---
-    for (int it = lane; it < 3 * T.npart_s; it += LHIP_NL) {
+    if (shortw) for (int it = lane; it < 3 * T.npart_s; it += LHIP_NL) {
         const int sblock = it / T.npart_s, b = it - sblock * T.npart_s;
         double ebb = 0;
         int j = T.lineoff_s[b];
@@ -574,7 +604,7 @@ psya_tail:
     }
     // --- short spreading (compute_masking_s second loop before limiting, 752-760) ---
     // lane = partition; its spreading row is fetched once (independent loads) and applied to the three sub-blocks
-    for (int b = lane; b < CBANDS; b += LHIP_NL) {
+    if (shortw) for (int b = lane; b < CBANDS; b += LHIP_NL) {
         float ecbv[3] = {0.f, 0.f, 0.f}, ebv[3] = {0.f, 0.f, 0.f};
         if (b < T.npart_s) {
             enum { MT = 12 };                         // rows are at most 12 long for every MPEG-1 rate; longer rows take the tail loop
@@ -938,7 +968,9 @@ LHIP_DEV double ns_interp(double x, double y, double r) {
 // resv_size / resv_max (bit reservoir only): ResvSize / ResvMax as the previous frame left them -- handed in by the caller, which knows
 // where the stream's reservoir record lives (the persistent per-stream kernel keeps it in LDS and pipelines the previous frame's bit
 // packing with this call, so this function must not read the record itself)
-template <int NCH> LHIP_DEV void kb_psyB(const Tables& T, const PowBase& pb10, const Workspace& W, const StreamDesc* SD, int gslot, int lane, PsyBLdsT<NCH>& L, int par = -1,
+// LAZY = 1 (batches whose psyA ran lazily: reservoir disabled): the short limiting, convert_partition2scalefac_s and the short pre-echo control only where
+// psy_need_s says the call's short thresholds are read; elsewhere the E_EN_S / E_THM_S entries of W.E are written as zeros.
+template <int NCH, int LAZY = 0> LHIP_DEV void kb_psyB(const Tables& T, const PowBase& pb10, const Workspace& W, const StreamDesc* SD, int gslot, int lane, PsyBLdsT<NCH>& L, int par = -1,
                                          int resv_size = 0, int resv_max = 0) {
     const int C = T.channels_out, Cp = T.psy_channels;      // Cp <= NCH: the launch picks the instantiation by Tables::psy_channels
     const int st = W.gslot_stream[gslot];
@@ -946,6 +978,7 @@ template <int NCH> LHIP_DEV void kb_psyB(const Tables& T, const PowBase& pb10, c
     const int q = gslot - sd.gslot0 - 1;
     if (q < 0) return;
     if (par >= 0 && q % T.mode_gr != par) return;
+    const bool shortw = LAZY ? psy_need_s(T, W, sd, gslot) != 0 : true;
     // PsyModel.js:1036-1038: share of the reservoir in use, as the previous frame left it (0 with the reservoir disabled)
     double pcfact = 0.0;
     if (!T.disable_reservoir) pcfact = resv_max == 0 ? 0.0 : (double)resv_size / resv_max * 0.5;
@@ -990,7 +1023,7 @@ template <int NCH> LHIP_DEV void kb_psyB(const Tables& T, const PowBase& pb10, c
         wave_sync();                                  // the next channel refills ebm
     }
     // (the spreading rows are dead: their LDS is thr_s / E from here on)
-    for (int ch = 0; ch < Cp; ch++) {
+    if (shortw) for (int ch = 0; ch < Cp; ch++) {
         const int64_t o = (int64_t)gslot * Cp + ch;
         // short-block limiting by the two previous sub-blocks (compute_masking_s, 762-775)
         const int pshort = W.prev_short[(int64_t)gslot * C + (ch & 1)];      // blocktype_old[chn & 1] (PsyModel.js:767)
@@ -1046,7 +1079,8 @@ template <int NCH> LHIP_DEV void kb_psyB(const Tables& T, const PowBase& pb10, c
             Eo[E_THM_L + sb] = thm_f;
         }
         // convert_partition2scalefac_s (644-687)
-        for (int it = lane; it < 3 * SBMAX_s; it += LHIP_NL) {
+        if (!shortw) for (int it = lane; it < 3 * SBMAX_s; it += LHIP_NL) { Eo[E_EN_S + it] = 0.f; Eo[E_THM_S + it] = 0.f; }
+        if (shortw) for (int it = lane; it < 3 * SBMAX_s; it += LHIP_NL) {
             const int sblock = it / SBMAX_s, sb = it - sblock * SBMAX_s;
             const float* ebs = W.eb_s + o * EBS_STRIDE + sblock * CBANDS;
             const float* thr = L.thr_s[ch][sblock];
@@ -1077,7 +1111,7 @@ template <int NCH> LHIP_DEV void kb_psyB(const Tables& T, const PowBase& pb10, c
         }
     }
     wave_sync();
-    for (int ch = 0; ch < Cp; ch++) {
+    if (shortw) for (int ch = 0; ch < Cp; ch++) {
         // short-block pre-echo control (PsyModel.js:1226-1267), one lane per band, the three sub-blocks in order: x0.8, the two
         // attack-driven interpolations towards the previous sub-block's finished threshold (sub-block 0: the previous CALL's
         // sub-block 2) -- identities when pcfact == 0 -- and the pulse halving.  ns_attacks holds only 0 / 1, so
@@ -1105,11 +1139,12 @@ template <int NCH> LHIP_DEV void kb_psyB(const Tables& T, const PowBase& pb10, c
         }
     }
     wave_sync();
+    const int nthm = shortw ? SBMAX_l + 3 * SBMAX_s : SBMAX_l;      // thresholds the channel-mixing steps below go over
     // inter-channel masking (PsyModel.js:525-543): stereo mode with ratio > 0
     if ((T.mode == 0 || T.mode == 1) && T.interChRatio > 0.0 && C > 1) {
         const double r_ = T.interChRatio;
         float nl[2] = {0.f, 0.f};
-        for (int i = lane; i < SBMAX_l + 3 * SBMAX_s; i += LHIP_NL) {
+        for (int i = lane; i < nthm; i += LHIP_NL) {
             const int idx = E_THM_L + i;                       // thm.l then thm.s are contiguous
             const double l = L.E[0][idx], r = L.E[1][idx];
             nl[0] = (float)(l + r * r_);
@@ -1127,7 +1162,7 @@ template <int NCH> LHIP_DEV void kb_psyB(const Tables& T, const PowBase& pb10, c
         const bool do_ns = d_abs(msfix) > 0.0;
         const double athlower_l = do_ns ? v8_pow_base(pb10, T.ATHlower * ath_adjust) : 0.0;
         const double athlower_s = athlower_l * ((double)BLKSIZE_s / BLKSIZE);
-        for (int i = lane; i < SBMAX_l + 3 * SBMAX_s; i += LHIP_NL) {
+        for (int i = lane; i < nthm; i += LHIP_NL) {
             const int it = E_THM_L + i, ie = E_EN_L + i;
             const bool lng = i < SBMAX_l;
             const int sb = lng ? i : (i - SBMAX_l) / 3;

@@ -698,7 +698,8 @@ int64_t lhip_debug_read(int what, void* dst, size_t cap) {
     if (what == 9) { const size_t n = cap < sizeof g_call_prof ? cap : sizeof g_call_prof; memcpy(dst, g_call_prof, n); return (int64_t)n; }
 #endif
     Context* ctx = nullptr;
-    { std::lock_guard<std::mutex> lk(g_ctx_mu); for (auto& kv : g_ctx) if (kv.second->ws.have_last) ctx = kv.second.get(); }
+    // (the most recent batch of the process, whichever context ran it: walking the contexts for one that has run a batch found a released aliased context's stale workspace)
+    { std::lock_guard<std::mutex> lk(g_ctx_mu); ctx = g_last_batch_ctx; }
     if (!ctx) { set_err("no batch has run"); return LHIP_ERR_INTERNAL; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     rt::set_device(ctx->device);

@@ -121,6 +121,7 @@ struct CallLayout {
 struct BatchPlan {
     TableSet* ts = nullptr;
     bool dev_io = false, resv = false, count_rej = false, use_frame = false, small = false;
+    bool psy_lazy = false;                         // a large batch without the bit reservoir on the separate kernels: psyA in two parts around the scans, the short-block side only where it is read (plan_batch)
     bool count_f32 = false;                        // ... of count_rej: Float32 samples, counted by g_count_rejected (the WAV float types are counted where they are converted)
     // WAV sample types (k_ingest.h): streams whose samples g_ingest converts, its grid, the floats of all planes, the descriptors on the device
     int ingest = 0, ingest_tiles = 0; size_t ingest_floats = 0; const IngestDesc* dING = nullptr;
@@ -193,6 +194,17 @@ static bool plan_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, BatchP
     // (one workgroup per stream at one wave per SIMD: beyond one stream per CU the separate kernels, each at full occupancy, are faster --
     //  bit-reservoir mode over 2048 streams: 0.7 M frames/s with this kernel, measured; the launch set of the separate kernels costs ~0.5 ms whatever S)
     P.use_frame = P.maxF <= 1 && !no_frame && S <= ctx->num_cus;
+    // Short-block psychoacoustics only where a short granule (or the stream state) reads them: that needs the block types, so psyA runs in two launches around
+    // the scans and reads its window twice -- worth it from a throughput-sized batch on (6 x CUs frame slots, where the quantization leaves the pair kernel; never
+    // below 1024), and not with the bit reservoir, whose short pre-echo control reads the previous call's short thresholds whatever the block type.  Below the
+    // threshold W.E holds all 122 entries of every call (lhip_debug_read(2)); in a lazy batch the short entries of a call nobody reads them from are zero.
+    // LAMEJS_PSY_LAZY_MIN_FRAMES=<n> (read per batch; a test hook): the threshold in frame slots -- 0: always, a huge value: never.
+    {
+        const char* e = getenv("LAMEJS_PSY_LAZY_MIN_FRAMES");
+        int64_t thr = 6 * (int64_t)ctx->num_cus < 1024 ? 1024 : 6 * (int64_t)ctx->num_cus;
+        if (e && *e) { thr = atoll(e); if (thr < 0) thr = 0; }
+        P.psy_lazy = !P.use_frame && !resv && (int64_t)P.nfs >= thr;
+    }
     return true;
 }
 // every workspace array once: the buffer grows to `bytes` and W.name points at it
@@ -486,5 +498,6 @@ static bool run_batch(Context* ctx, std::vector<Job>& jobs, bool dev_io, bool wa
     g_stat_frames = P.nfr; g_stat_repaired = P.repaired; g_stat_iters = P.iters; g_last_paths = P.paths; g_last_quant = P.ql;
     WorkSet& ws = ctx->ws;
     ws.lastW = P.W; ws.lastC = P.ts->T.channels_out; ws.lastCp = P.ts->T.psy_channels; ws.have_last = true;
+    { std::lock_guard<std::mutex> lk(g_ctx_mu); g_last_batch_ctx = ctx; }
     return true;
 }

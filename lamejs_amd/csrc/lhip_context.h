@@ -73,6 +73,7 @@ struct Context {
 
 static std::mutex g_ctx_mu;
 static std::map<int, std::unique_ptr<Context>> g_ctx;
+static Context* g_last_batch_ctx = nullptr;      // the context of the process's most recent batch (under g_ctx_mu; contexts are never destroyed): what lhip_debug_read taps
 
 static Context* get_context(int device) {
     std::lock_guard<std::mutex> lk(g_ctx_mu);

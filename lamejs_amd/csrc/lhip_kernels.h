@@ -32,11 +32,13 @@ static __device__ __forceinline__ int xcd_wave_item(int n, int* lane) {
     return (g >= 0 && it < n) ? it : -1;
 }
 #define WAVE_LDS(TYPE, NAME) __shared__ TYPE NAME##_[WPB]; TYPE& NAME = NAME##_[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))]
-__global__ __launch_bounds__(64 * WPB) void g_psyA(Tables T, Workspace W, const StreamDesc* SD, const StreamIO* IO, int chn0, int nch) {
+// PART 0: all of kb_psyA in one launch.  A lazy batch (BatchPlan::psy_lazy) launches PART 1 (high-pass + sub-block peaks: all the scans need), the scans,
+// and then PART 2 in its lazy form, which knows the block types and leaves out the short-block side nobody reads.
+template <int PART> __global__ __launch_bounds__(64 * WPB) void g_psyA(Tables T, Workspace W, const StreamDesc* SD, const StreamIO* IO, int chn0, int nch) {
     WAVE_LDS(PsyALds, L);
     int lane;
     const int it = xcd_wave_item(W.ngslots * nch, &lane);
-    if (it >= 0) kb_psyA(T, W, SD, IO, it / nch, chn0 + it % nch, lane, L);
+    if (it >= 0) kb_psyA<PART, PART == 2>(T, W, SD, IO, it / nch, chn0 + it % nch, lane, L);
 }
 __global__ __launch_bounds__(256) void g_prep(Tables T, Workspace W, const StreamDesc* SD, const StreamIO* IO, int nstreams) {
     kb_prep(T, W, SD, IO, nstreams, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
@@ -49,11 +51,11 @@ __global__ __launch_bounds__(64) void g_scan_raw(Tables T, Workspace W, const St
 __global__ __launch_bounds__(64) void g_scan_attack(Tables T, Workspace W, const StreamDesc* SD, int ngs) { const int g = blockIdx.x * 64 + threadIdx.x; if (g < ngs) kb_scan_attack(T, W, SD, g); }
 __global__ __launch_bounds__(64) void g_scan_blocktype(Tables T, Workspace W, const StreamDesc* SD, int ngs) { const int g = blockIdx.x * 64 + threadIdx.x; if (g < ngs) kb_scan_blocktype(T, W, SD, g); }
 __global__ __launch_bounds__(ATH_NT) void g_scan_ath(Tables T, Workspace W, const StreamDesc* SD) { __shared__ AthLds L; kb_scan_ath(T, W, SD, blockIdx.x, threadIdx.x, L); }
-template <int NCH> __global__ __launch_bounds__(64 * WPB) void g_psyB(Tables T, PowBase pb, Workspace W, const StreamDesc* SD, int par) {
+template <int NCH, int LAZY> __global__ __launch_bounds__(64 * WPB) void g_psyB(Tables T, PowBase pb, Workspace W, const StreamDesc* SD, int par) {
     WAVE_LDS(PsyBLdsT<NCH>, L);
     int lane;
     const int it = xcd_wave_item(W.ngslots, &lane);
-    if (it >= 0) kb_psyB<NCH>(T, pb, W, SD, it, lane, L, par);
+    if (it >= 0) kb_psyB<NCH, LAZY>(T, pb, W, SD, it, lane, L, par);
 }
 __global__ __launch_bounds__(64, 4) void g_poly(Tables T, Workspace W, const StreamDesc* SD, const StreamIO* IO, int nitems) {
     __shared__ PolyLds L;

@@ -53,11 +53,23 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
         if (nb < 1) nb = 1;
         LAUNCHB(KT_PREP, g_prep, (int)nb, 256, st, T, W, dSD, dIO, S);
     }
-    LAUNCHB(KT_PSYA, g_psyA, XCD_GRID_W(ngs * C), 64 * WPB, st, T, W, dSD, dIO, 0, C);
-    if (T.psy_channels == 4) LAUNCHB(KT_PSYA, g_psyA, XCD_GRID_W(ngs * 2), 64 * WPB, st, T, W, dSD, dIO, 2, 2);
+    // A lazy batch (plan_batch) runs the high-pass + sub-block peaks first, then the scans, and everything else of psyA once the block types are known:
+    // the short-block side is then computed only for the calls a short granule (or the stream state) reads it from
+    const bool lazy = P.psy_lazy;
+    if (lazy) {
+        LAUNCHB(KT_PSYA, g_psyA<1>, XCD_GRID_W(ngs * C), 64 * WPB, st, T, W, dSD, dIO, 0, C);
+        if (T.psy_channels == 4) LAUNCHB(KT_PSYA, g_psyA<1>, XCD_GRID_W(ngs * 2), 64 * WPB, st, T, W, dSD, dIO, 2, 2);
+    } else {
+        LAUNCHB(KT_PSYA, g_psyA<0>, XCD_GRID_W(ngs * C), 64 * WPB, st, T, W, dSD, dIO, 0, C);
+        if (T.psy_channels == 4) LAUNCHB(KT_PSYA, g_psyA<0>, XCD_GRID_W(ngs * 2), 64 * WPB, st, T, W, dSD, dIO, 2, 2);
+    }
     LAUNCH(KT_SCAN, g_scan_raw, (ngs + 63) / 64, st, T, W, dSD, ngs);
     LAUNCH(KT_SCAN, g_scan_attack, (ngs + 63) / 64, st, T, W, dSD, ngs);
     LAUNCH(KT_SCAN, g_scan_blocktype, (ngs + 63) / 64, st, T, W, dSD, ngs);
+    if (lazy) {
+        LAUNCHB(KT_PSYA, g_psyA<2>, XCD_GRID_W(ngs * C), 64 * WPB, st, T, W, dSD, dIO, 0, C);
+        if (T.psy_channels == 4) LAUNCHB(KT_PSYA, g_psyA<2>, XCD_GRID_W(ngs * 2), 64 * WPB, st, T, W, dSD, dIO, 2, 2);
+    }
     // g_scan_ath (needs psyA's loudness, feeds psyB and the quantizer) is one workgroup per stream: it runs on a side
     // stream while polyphase + MDCT (which need neither) keep the chip busy.  With per-kernel timing on, everything stays
     // on the launch stream so that the HIP events bracket each kernel.
@@ -93,8 +105,8 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
         P.paths |= qa.ctr ? LHIP_PATH_RESV_STREAM_HELPERS : LHIP_PATH_RESV_STREAM_NOHELPERS;
         LAUNCHB(KT_QUANT, g_resv_stream, S, 64 * RS_WAVES, st, qa);
     } else {
-    if (T.psy_channels == 4) LAUNCHB(KT_PSYB, g_psyB<4>, XCD_GRID_W(ngs), 64 * WPB, st, T, ts.pb10, W, dSD, -1);
-    else LAUNCHB(KT_PSYB, g_psyB<2>, XCD_GRID_W(ngs), 64 * WPB, st, T, ts.pb10, W, dSD, -1);
+    if (T.psy_channels == 4) { if (lazy) LAUNCHB(KT_PSYB, (g_psyB<4, 1>), XCD_GRID_W(ngs), 64 * WPB, st, T, ts.pb10, W, dSD, -1); else LAUNCHB(KT_PSYB, (g_psyB<4, 0>), XCD_GRID_W(ngs), 64 * WPB, st, T, ts.pb10, W, dSD, -1); }
+    else { if (lazy) LAUNCHB(KT_PSYB, (g_psyB<2, 1>), XCD_GRID_W(ngs), 64 * WPB, st, T, ts.pb10, W, dSD, -1); else LAUNCHB(KT_PSYB, (g_psyB<2, 0>), XCD_GRID_W(ngs), 64 * WPB, st, T, ts.pb10, W, dSD, -1); }
     // persistent quantization kernels: as many workgroups as can be resident (2 per CU), frames dispensed dynamically
     int qgrid = (nfs + QWAVES - 1) / QWAVES;
     if (qgrid > ctx->num_cus * 2) qgrid = ctx->num_cus * 2;

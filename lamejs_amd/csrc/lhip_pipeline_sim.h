@@ -86,17 +86,28 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     P.paths |= LHIP_PATH_SEPARATE | (T.rs_ratio != 1 ? LHIP_PATH_PREP : 0) | (T.psy_channels == 4 ? LHIP_PATH_PSY4 : 0);
     for (int s = 0; s < S; s++) WAVE_RUN(kb_load(T, W, dSD, dIO, s, lane_));
     if (T.rs_ratio != 1) kb_prep(T, W, dSD, dIO, S, 0, 1);
-    for (int b = 0; b < ngs * C; b++) WAVE_RUN(kb_psyA(T, W, dSD, dIO, b / C, b % C, lane_, LA));
-    if (T.psy_channels == 4) for (int b = 0; b < ngs * 2; b++) WAVE_RUN(kb_psyA(T, W, dSD, dIO, b / 2, 2 + b % 2, lane_, LA));
+    const bool lazy = P.psy_lazy;      // (as lhip_pipeline_hip.h: part 1, the scans, then part 2 in its lazy form)
+    if (lazy) {
+        for (int b = 0; b < ngs * C; b++) WAVE_RUN(kb_psyA<1>(T, W, dSD, dIO, b / C, b % C, lane_, LA));
+        if (T.psy_channels == 4) for (int b = 0; b < ngs * 2; b++) WAVE_RUN(kb_psyA<1>(T, W, dSD, dIO, b / 2, 2 + b % 2, lane_, LA));
+    } else {
+        for (int b = 0; b < ngs * C; b++) WAVE_RUN(kb_psyA(T, W, dSD, dIO, b / C, b % C, lane_, LA));
+        if (T.psy_channels == 4) for (int b = 0; b < ngs * 2; b++) WAVE_RUN(kb_psyA(T, W, dSD, dIO, b / 2, 2 + b % 2, lane_, LA));
+    }
     for (int b = 0; b < ngs; b++) kb_scan_raw(T, W, dSD, b);
     for (int b = 0; b < ngs; b++) kb_scan_attack(T, W, dSD, b);
     for (int b = 0; b < ngs; b++) kb_scan_blocktype(T, W, dSD, b);
+    if (lazy) {
+        for (int b = 0; b < ngs * C; b++) WAVE_RUN((kb_psyA<2, 1>(T, W, dSD, dIO, b / C, b % C, lane_, LA)));
+        if (T.psy_channels == 4) for (int b = 0; b < ngs * 2; b++) WAVE_RUN((kb_psyA<2, 1>(T, W, dSD, dIO, b / 2, 2 + b % 2, lane_, LA)));
+    }
 #ifdef LHIP_WAVESIM
     { static thread_local AthLds LAth; for (int s = 0; s < S; s++) wsim::run_block(ATH_NT / 64, [&](int wave_, int lane_) { kb_scan_ath(T, W, dSD, s, 64 * wave_ + lane_, LAth); }); }
 #else
     { static thread_local AthLds LAth; for (int s = 0; s < S; s++) kb_scan_ath(T, W, dSD, s, 0, LAth); }
 #endif
-    if (!resv) for (int b = 0; b < ngs; b++) WAVE_RUN(kb_psyB<4>(T, ts.pb10, W, dSD, b, lane_, LB, -1));
+    if (!resv && lazy) for (int b = 0; b < ngs; b++) WAVE_RUN((kb_psyB<4, 1>(T, ts.pb10, W, dSD, b, lane_, LB, -1)));
+    else if (!resv) for (int b = 0; b < ngs; b++) WAVE_RUN(kb_psyB<4>(T, ts.pb10, W, dSD, b, lane_, LB, -1));
     for (int b = 0; b < (ngs * C + POLY_PER_WAVE - 1) / POLY_PER_WAVE; b++) WAVE_RUN(kb_polyphase(T, W, dSD, dIO, b, ngs * C, lane_, LP));
     for (int b = 0; b < ngs; b++) WAVE_RUN(kb_mdct(T, W, dSD, b, lane_, LM));
     if (resv) {
