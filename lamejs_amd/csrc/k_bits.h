@@ -10,7 +10,7 @@
 #include "lhip_defs.h"
 #include "lhip_wave.h"
 #include "lhip_layout.h"
-#include "k_quant.h"   // frame_bits_of / frame_padding
+#include "k_quant_framebits.h"   // frame_bits_of / frame_padding
 
 namespace lhip {
 

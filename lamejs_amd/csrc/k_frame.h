@@ -204,7 +204,7 @@ enum { RS_PSYB0, RS_QUANT, RS_STAGES, RS_WAVES = 4,
                                                                 : (sizeof(PsyBLds4) > sizeof(BitsLds) ? sizeof(PsyBLds4) : sizeof(BitsLds))) + 15) & ~15 };
 // stage `stage` of frame k (of F) of stream st for wave wv; k == F: only the tail (bit packing of the last frame)
 // cshare (device, wave simulation): the count helpers' records -- while a frame is quantized the psyB and the bit-packing wave have nothing to do
-// and take the Huffman counts of waves 0 / 1 (q_count_helper, k_quant.h)
+// and take the Huffman counts of waves 0 / 1 (q_count_helper, k_quant_helper.h)
 template <int PAIRQ>
 LHIP_DEV void kb_resv_stage(int stage, const Tables& T, const PowBase& pb, const Workspace& W, const StreamDesc* SD, int st, int k, int F,
                             int wv, int lane, unsigned char* lds, QuantTabs& Q, int* mbox, ResvState& RV, int32_t* nout, CountShare* cshare = nullptr) {

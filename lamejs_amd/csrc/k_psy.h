@@ -28,15 +28,10 @@ namespace lhip {
 // of the k1 = 4 pass spread over all 32 banks.  Everything that reads or writes transform DATA goes through fzp(): the windowing's outputs,
 // the passes, the energies' operands, the joint-stereo copies; the other phases use the same memory as plain scratch, and every transition
 // between the two views already goes through registers and a wave_sync.
-#ifdef LHIP_NO_FZ_PAD      /* A/B builds: the plain layout */
-LHIP_DEV int fzp(int a) { return a; }
-LHIP_DEV int fzo(int c) { return c; }
-#else
 LHIP_DEV int fzp(int a) { return a + (a >> 5); }
 // offsets inside an item: index + c lands at fzp(index) + c + c / 32 because (index & 31) + (c & 31) < 32 for every operand of every pass
 // (k1 = 4: a 16-aligned group; k1 = 16: i < 16 and c & 31 is 0 or 16; k1 >= 64: c is a multiple of 32)
 LHIP_DEV int fzo(int c) { return c + (c >> 5); }
-#endif
 LHIP_DEV void fht_item0(float* fz, int base, int k1, int kx, int m) {
     const int k2 = k1 << 1, k3 = k2 + k1, k4 = k2 << 1;
     const int K1 = fzo(k1), K2 = fzo(k2), K3 = fzo(k3);
@@ -511,7 +506,7 @@ psya_tail:
 #else
     {
         // The partitions tile the 513 lines, and a partition's energy is the f64 sum of its lines in ascending order: a systolic fold
-        // (as calc_noise's band sums, k_quant.h) -- lane l owns the lines 8 l .. 8 l + 7 and folds them, in order, onto the running sum
+        // (as calc_noise's band sums, k_quant_noise.h) -- lane l owns the lines 8 l .. 8 l + 7 and folds them, in order, onto the running sum
         // lane l - 1 hands over, the chain restarting at every partition's first line; ceil(longest partition / 8) + 1 hand-overs give
         // every partition's strictly sequential sum (one lane per partition walking its lines took as many trips as the longest
         // partition has lines: 83 at 44.1 kHz).  Line 512 is added by lane 63 at the end -- it is the last line of the last partition.

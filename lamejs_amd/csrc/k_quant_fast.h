@@ -1,11 +1,11 @@
 // k_quant_fast.h -- the speculative quantization pass of a FAST table set (quality 7, LAME's -f: noise_shaping == 0 and use_best_huffman == 0):
 // the reference's outer_loop returns right after bin_search_StepSize (Quantize.js:886-888) and iteration_finish_one has no best_huffman_divide.
 //
-// The general program (k_quant.h: q_unit / q_outer_loop) computes exactly that for such a table set -- it reads the switches -- but it is one body for
+// The general program (k_quant.h, k_quant_search.h: q_unit / q_outer_loop) computes exactly that for such a table set -- it reads the switches -- but it is one body for
 // every setting: the noise loop, the amplification, the Huffman region search and the count helpers are compiled into every kernel that holds it, and
 // they set its registers and its code size.  This file is the same granule-channel with nothing but what the fast mode runs, built from the q_*
 // functions of k_quant.h by calling them: load the lines, x^(3/4) and the energy test, what calc_xmin leaves behind that quantization reads
-// (q_fast_limits), the bin search over count_bits with all-zero scalefactors (q_bin_search), best_scalefac_store / scfsi, the record.  It leaves
+// (q_search_limits), the bin search over count_bits with all-zero scalefactors (q_bin_search), best_scalefac_store / scfsi, the record.  It leaves
 // GrSide, the bin-search memo (bs_tab, bs_asg, bs_ntab, bs_state) and the digest words (W.vdig) exactly as q_unit / q_outer_loop leave them, so
 // g_validate_fast, g_fixup (whose repair pass keeps the general body) and g_bits run behind it unchanged.
 //
@@ -15,25 +15,6 @@
 // (g_quant_fast, lhip_kernels.h); pairs do not wait for each other: no workgroup barrier inside the frame loop.
 #pragma once
 namespace lhip {
-
-// What calc_xmin (QuantizePVT.js:569-719, q_calc_xmin) leaves behind that quantization reads: max_nonzero_coeff, and this code base's two facts derived
-// with it -- the first band reaching past it (q_set_firstcut) and "the lines 512..575 are all zero" (GI::tail0).  The thresholds themselves (L.xmin,
-// L.rxmin) are read by calc_noise alone, which a fast table set never calls.
-LHIP_DEV void q_fast_limits(GI& g, int lane, QuantLds& L, const int want_tail0) {
-    lane = fresh_lane(lane);
-    if (g.block_type != SHORT_TYPE) {
-        int t = -1;
-        for (int k = lane; k < 576; k += LHIP_NL) if (!((double)L.xr[k] == 0)) t = k;
-        t = wave_max(t);
-        g.max_nonzero_coeff = (t >= 575) ? 575 : t + 1;
-        if (want_tail0) g.tail0 = t < 512;
-    } else {
-        g.max_nonzero_coeff = 575;
-        if (want_tail0) g.tail0 = q_tail_is_zero(lane, L);
-    }
-    q_set_firstcut(g, lane, L);
-    wave_sync();
-}
 
 // bin_search_StepSize (Quantize.js:322-381) and nothing behind it: the two states ST_BS / ST_BSUP of q_outer_loop, on the granule state itself (the
 // general loop works on a copy, cod_info_w, and copies it back when noise_shaping == 0).  The working spectrum L.ixw ends as the quantization at the
@@ -53,44 +34,12 @@ LHIP_DEV void q_bin_search(const Tables& T, GI& g, int targ_bits, int bs_start, 
         int asg = 0;
         const int nBits = q_count_bits_rounds<SKIP>(T, g, L.sfw, L.ixw, 0, pn, &asg, lane, L, Q);
         if (nbs < BS_TAB_MAX) { if (lane == 0) { L.memo.bs_tab[nbs] = (g.global_gain << 24) | nBits; L.memo.bs_asg[nbs] = asg; } nbs++; }
-        if (!up) {
-            if (CurrentStep == 1 || nBits == desired_rate) up = 1;
-            else {
-                int step;
-                if (nBits > desired_rate) {
-                    if (Direction == 2) flagGoneOver = 1;
-                    if (flagGoneOver) CurrentStep /= 2;
-                    Direction = 1;
-                    step = CurrentStep;
-                } else {
-                    if (Direction == 1) flagGoneOver = 1;
-                    if (flagGoneOver) CurrentStep /= 2;
-                    Direction = 2;
-                    step = -CurrentStep;
-                }
-                g.global_gain += step;
-                if (g.global_gain < 0) { g.global_gain = 0; flagGoneOver = 1; }
-                if (g.global_gain > 255) { g.global_gain = 255; flagGoneOver = 1; }
-                continue;
-            }
-        }
-        if (nBits > desired_rate && g.global_gain < 255) { g.global_gain++; continue; }
+        if (bs_advance(nBits, desired_rate, g.global_gain, CurrentStep, flagGoneOver, Direction, up)) continue;
         g.part2_3_length = nBits;
         break;
     }
     *bs_gain_out = g.global_gain;                            // OldValue[ch] after this granule
-    wave_sync();
-    LHIP_LANE_ONCE(i, 0, nbs) {
-        const int32_t e = L.memo.bs_tab[i], a = L.memo.bs_asg[i];
-        rec->bs_tab[i] = e; rec->bs_asg[i] = a;
-        if (i < VD_ENT) { dig[(VD_TAB + 2 * i) * dn] = (uint32_t)e; dig[(VD_TAB + 2 * i + 1) * dn] = (uint32_t)a; }
-    }
-    if (lane == 0) {
-        const int state = pack_cond_fields(g, 0);
-        rec->bs_ntab = nbs; rec->bs_state = state;
-        dig[VD_TARG * dn] = (uint32_t)targ_bits | ((uint32_t)nbs << 24); dig[VD_STATE * dn] = (uint32_t)state;
-    }
-    wave_sync();
+    q_flush_bs_memo(g, targ_bits, nbs, rec, dig, dn, lane, L);
 }
 
 // One granule-channel of a fast table set, from the spectrum to the published record: q_unit without what such a table set never runs.
@@ -110,7 +59,7 @@ LHIP_DEV UnitOut q_unit_fast(const Tables& T, const PowBase& pb10, const Workspa
     GrSide* out = W.side + ((int64_t)fidx * 2 + gr) * C + ch;
     if (q_init_xrpow(g, lane, L, Q)) {
         active = 1;
-        q_fast_limits(g, lane, L, SKIP);
+        q_search_limits(g, lane, L, SKIP);
         if constexpr (SKIP != 0) {
             if (g.tail0) { for (int i = 256 + lane; i < 288; i += LHIP_NL) ((uint32_t*)L.ixw)[i] = 0u; wave_sync(); }
         }
@@ -129,7 +78,7 @@ LHIP_DEV UnitOut q_unit_fast(const Tables& T, const PowBase& pb10, const Workspa
     u.bits = g.part2_3_length + g.part2_length;
     u.block_type = g.block_type;
     if (gr == 0) { LHIP_LANE_ONCE(i, 0, (SFBMAX) + 1) L.sf_gr0[ch][i] = (int8_t)L.sfb[i]; }
-    // ---- publish the record and the signed quantized spectrum (q_unit's) ----
+    // ---- publish the record and the signed quantized spectrum: q_unit's statements (k_quant.h), a second copy to be changed with them (see there) ----
     lane = lane_anew(lane);
     if (lane == 0) {
         out->part2_3_length = g.part2_3_length; out->part2_length = g.part2_length; out->big_values = g.big_values;

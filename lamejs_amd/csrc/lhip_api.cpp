@@ -685,11 +685,11 @@ int64_t lhip_debug_read(int what, void* dst, size_t cap) {
         const size_t n = cap < sizeof g_last_quant ? cap : sizeof g_last_quant; memcpy(dst, &g_last_quant, n); return (int64_t)n;
     }
 #ifdef LHIP_HOSTSIM
-    if (what == 10) {                                   // evaluations so far with the short / the full round count (RoundStats, k_quant.h)
+    if (what == 10) {                                   // evaluations so far with the short / the full round count (RoundStats, k_quant_prof.h)
         const int64_t v[2] = {(int64_t)__atomic_load_n(&round_stats().head, __ATOMIC_RELAXED), (int64_t)__atomic_load_n(&round_stats().full, __ATOMIC_RELAXED)};
         const size_t n = cap < sizeof v ? cap : sizeof v; memcpy(dst, v, n); return (int64_t)n;
     }
-    if (what == 12) {                                   // calc_noise calls so far with 7 / with 9 / with 3 lines per lane (NoiseLineStats, k_quant.h; the 64-lane simulation counts)
+    if (what == 12) {                                   // calc_noise calls so far with 7 / with 9 / with 3 lines per lane (NoiseLineStats, k_quant_prof.h; the 64-lane simulation counts)
         const int64_t v[3] = {(int64_t)__atomic_load_n(&noise_line_stats().n7, __ATOMIC_RELAXED), (int64_t)__atomic_load_n(&noise_line_stats().n9, __ATOMIC_RELAXED), (int64_t)__atomic_load_n(&noise_line_stats().n3, __ATOMIC_RELAXED)};
         const size_t n = cap < sizeof v ? cap : sizeof v; memcpy(dst, v, n); return (int64_t)n;
     }

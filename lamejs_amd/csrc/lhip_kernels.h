@@ -86,15 +86,9 @@ LHIP_DEV int next_frame_slot(int32_t* ctr) {
     return __builtin_amdgcn_readfirstlane(v);
 }
 struct QArgs { Tables T; PowBase pb; Workspace W; const StreamDesc* SD; int chain, nfs, ctr; };
-#ifdef LHIP_QVGPR      /* experiment builds only: cap g_quant's register budget at what 5 / 6 waves per SIMD would leave it (96 / 80).  The backend doubles an
-                          "amdgpu-num-vgpr" request on gfx90a+ (unified VGPR + AGPR file) and clamps it to the range the waves-per-EU bounds imply, so the upper
-                          bound must be opened too */
-#define LHIP_QUANT_BOUNDS __attribute__((amdgpu_flat_work_group_size(1, 64 * QWAVES), amdgpu_waves_per_eu(LHIP_QOCC, 8), amdgpu_num_vgpr((LHIP_QVGPR) / 2)))
-#else
 #define LHIP_QUANT_BOUNDS __launch_bounds__(64 * QWAVES, LHIP_QOCC)
-#endif
 // SKIP: the batch kernels exist in two forms -- with the search's dead last round of pairs skipped where the granule-channel's spectrum allows it (GI::tail0,
-// k_quant.h), and without any of that code: the host launches the second where the configuration's lowpass leaves lines above 512 in every long block (320 kbps),
+// k_quant_count.h), and without any of that code: the host launches the second where the configuration's lowpass leaves lines above 512 in every long block (320 kbps),
 // which would only carry the first form's larger code (measured: + 1 % of such a step)
 template <int RESV, int SKIP> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_unused) {
     __shared__ QuantTabs Q;

@@ -270,7 +270,7 @@ static bool derive_index_tables(TableSet& ts, void* stream) {
         }
         memcpy(extra.data() + amp_at, amp, sizeof amp);
     }
-    // calc_noise's systolic fold (k_quant.h): lane l owns the lines n l .. n l + n - 1 of the (re-ordered) spectrum, n = noise_nln; per lane,
+    // calc_noise's systolic fold (k_quant_noise.h): lane l owns the lines n l .. n l + n - 1 of the (re-ordered) spectrum, n = noise_nln; per lane,
     // bit k = line n l + k is the first line of its scalefactor band, bit 16 + k = it is the last one ([0..63] long, [64..127] short blocks);
     // then the widest band among bands 0 .. b: 24 entries for long blocks, 40 for short ones (band = 3 * sfb + window).
     // noise_nln: calc_noise reads the sums of the bands below psymax only -- 21 long or 3 * 12 short ones, sfb21_extra being refused above --

@@ -371,7 +371,7 @@ LHIP_DEV double unid(double v) { union { double d; int i[2]; } u; u.d = v; u.i[0
 #endif
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Signalling between the waves of ONE workgroup through words in LDS (k_quant_tail.h: tail help; k_quant.h: count_bits on a second wave).
+// Signalling between the waves of ONE workgroup through words in LDS (k_quant_tail.h: tail help; k_quant_helper.h: count_bits on a second wave).
 // wg_store publishes everything the wave wrote to LDS before it; a wave that has seen the value calls wg_acquire before reading.
 // ---------------------------------------------------------------------------------------------------------------------
 #if defined(LHIP_HOSTSIM) && LHIP_NL == 1

@@ -59,7 +59,7 @@ CASES = [
 ]
 for _i, _c in enumerate(CASES):
     _c.setdefault("seed", SEED + _i)
-# quality 7: the fast unit has code of its own for the skipped round (q_fast_limits' tail0, the zeroing statement of q_unit_fast).  Each case is the twin of
+# quality 7: the fast unit has code of its own for the skipped round (q_search_limits' tail0, the zeroing statement of q_unit_fast).  Each case is the twin of
 # a quality-3 one: same configuration, same material, same seed.  `silence`: an inactive unit leaves an all-zero working spectrum in front of a four-round
 # unit of the same wave.
 Q7_TWINS = ("stereo128/fuzz", "stereo128/silence", "stereo320/fuzz", "lsf64/fuzz", "stereo32k96/fuzz", "mono32k48/fuzz")

@@ -4,7 +4,7 @@ import numpy as np
 
 
 def test_square_comparison_equals_sqrt_comparison_for_float32_operands():
-    """amp_scalefac_bands (lamejs_amd/csrc/k_quant.h): for Float32 d >= 0 and M > 1, d < sqrt(M) [f64, correctly rounded] <=> d * d < M [exact in f64]."""
+    """amp_scalefac_bands (lamejs_amd/csrc/k_quant_amp.h): for Float32 d >= 0 and M > 1, d < sqrt(M) [f64, correctly rounded] <=> d * d < M [exact in f64]."""
     rng = np.random.default_rng(3)
     M = np.concatenate([rng.uniform(1.0, 4.0, 400000), 10.0 ** rng.uniform(0, 12, 400000)]).astype(np.float32)
     M = M[M > 1.0]

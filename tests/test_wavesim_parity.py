@@ -172,7 +172,7 @@ def test_wavesim_tail_help():
 
 
 def test_wavesim_one_frame_launch_count_helpers():
-    """The one-frame launch as a real eight-wave workgroup (csrc/k_frame.h kb_frame_stage, k_quant.h q_count_helper / q_count_bits_piped; round 5): 1152
+    """The one-frame launch as a real eight-wave workgroup (csrc/k_frame.h kb_frame_stage, k_quant_helper.h q_count_helper / q_count_bits_piped; round 5): 1152
     samples per call -- the reference's documented call pattern -- on one- and two-channel streams, MPEG-1 and MPEG-2, joint stereo and the bit reservoir
     (whose multi-frame calls run the per-stream kernel with the same helpers).  Every call's bytes against the oracle, and both fates of a calc_noise made
     beside the helper's count -- committed, dropped because the evaluation did not fit -- must have occurred; so must a one-channel frame's wait for the

@@ -1,36 +1,32 @@
 #!/usr/bin/env python3
-"""DEV TOOL: static attribution of g_quant's ISA to k_quant.h source functions.
+"""DEV TOOL: static attribution of g_quant's ISA to the source functions of the quantization search (the k_quant*.h
+family).
 
-Build the listing first:
+Build the listing first (tools/isa_build.sh):
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -x hip --cuda-device-only -gline-tables-only -S lamejs_amd/csrc/lhip_api.cpp -o kg.s
-usage: isa_attrib.py kg.s [kernel-symbol-substring]
-Every instruction is attributed to the last `.loc` that pointed into k_quant.h (helpers inlined from lhip_wave.h /
+usage: isa_attrib.py kg.s [kernel-symbol-substring [anything: also the top lines]]
+Every instruction is attributed to the last `.loc` that pointed into one of those files (helpers inlined from lhip_wave.h /
 lhip_math.h are charged to their call site).  Prints VALU / SGPR-spill (v_readlane/v_writelane) / SALU / LDS / VMEM counts
 per source function (by line range) -- static counts, to be weighted with the phase call counts of phase_prof.py.
 """
 import re, sys, collections
+import quant_src
 path = sys.argv[1]
 kern = sys.argv[2] if len(sys.argv) > 2 else "g_quant"
-src = open("lamejs_amd/csrc/k_quant.h").read().split("\n")
-# function start lines
-funcs = []
-for i, l in enumerate(src, 1):
-    m = re.match(r"^(?:template.*)?LHIP_DEV\s+[\w:<>\*& ]+?\s+(\w+)\s*\(", l)
-    if m and not l.rstrip().endswith(";"):
-        funcs.append((i, m.group(1)))
-def func_of(line):
+funcs = quant_src.functions()
+def func_of(loc):
     name = "?"
-    for s, n in funcs:
-        if s <= line: name = n
+    for s, n in funcs[loc[0]] if loc else ():
+        if s <= loc[1]: name = n
         else: break
     return name
 lines = open(path).read().split("\n")
-fileno = None
+fileno = {}
 for l in lines:
-    m = re.match(r'\s*\.file\s+(\d+)\s+"[^"]*"\s+"k_quant\.h"', l)
-    if m: fileno = m.group(1)
+    m = re.match(r'\s*\.file\s+(\d+)\s+(?:"[^"]*"\s+)?"(?:[^"]*/)?(k_quant(?:_\w+)?\.h)"', l)      # (with or without a directory string)
+    if m and m.group(2) in funcs: fileno[m.group(1)] = m.group(2)
 inside = False
-cur = 0
+cur = None
 stat = collections.defaultdict(lambda: collections.Counter())
 perline = collections.defaultdict(lambda: collections.Counter())
 for l in lines:
@@ -41,7 +37,7 @@ for l in lines:
         break
     m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", l)
     if m:
-        if m.group(1) == fileno: cur = int(m.group(2))
+        if m.group(1) in fileno: cur = (fileno[m.group(1)], int(m.group(2)))
         continue
     m = re.match(r"\s+([a-z][a-z0-9_]+)", l)
     if not m: continue
@@ -62,5 +58,6 @@ for f, c in sorted(stat.items(), key=lambda kv: -(kv[1]["valu"] + kv[1]["spill"]
 print("%-28s %6d %6d %6d %5d %5d" % ("TOTAL", tot["valu"], tot["spill"], tot["salu"], tot["lds"], tot["vmem"]))
 if len(sys.argv) > 3:
     print("\nper line (top 60 by valu+spill):")
-    for ln, c in sorted(perline.items(), key=lambda kv: -(kv[1]["valu"] + kv[1]["spill"]))[:60]:
-        print("%5d %5d %5d %5d  %s" % (ln, c["valu"], c["spill"], c["salu"], src[ln - 1].strip()[:110] if 0 < ln <= len(src) else ""))
+    for loc, c in sorted(((k, v) for k, v in perline.items() if k), key=lambda kv: -(kv[1]["valu"] + kv[1]["spill"]))[:60]:
+        src = quant_src.source(loc[0])
+        print("%-24s %5d %5d %5d  %s" % ("%s:%d" % loc, c["valu"], c["spill"], c["salu"], src[loc[1] - 1].strip()[:110] if 0 < loc[1] <= len(src) else ""))

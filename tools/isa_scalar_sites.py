@@ -17,8 +17,8 @@ for l in open(path):
     if l.startswith(".Lfunc_end"): break
     m = re.match(r'\s*\.loc\s+(\d+)\s+(\d+)\s+\d+(.*)$', l)
     if m:
-        # innermost frame that lies in k_quant.h / k_quant_tail.h, else the .loc itself
-        mm = re.findall(r'(k_quant(?:_tail)?\.h):(\d+):', m.group(3))
+        # innermost frame that lies in k_quant.h or a k_quant_*.h file (the search's stages, k_quant_tail.h, k_quant_fast.h), else the .loc itself
+        mm = re.findall(r'\b(k_quant(?:_\w+)?\.h):(\d+):', m.group(3))
         cur = (mm[0][0], int(mm[0][1])) if mm else (files.get(m.group(1), '?').split('/')[-1], int(m.group(2)))
         continue
     m = re.match(r'\s+([a-z][a-z0-9_]+)\s*(.*)', l)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """DEV TOOL (CPU only): the shape of the quantization search per granule-channel on the bench materials -- bin-search depth, step-up evaluations, and the
-lengths of the `while (bits > huff_bits) gain++` runs of the outer loop -- from the one-lane host simulation (LAMEJS_SEARCH_STATS=1, k_quant.h SearchStats).
+lengths of the `while (bits > huff_bits) gain++` runs of the outer loop -- from the one-lane host simulation (LAMEJS_SEARCH_STATS=1, k_quant_prof.h SearchStats).
 Prices evaluating a run's gains side by side on idle waves of the one-frame launch (VERDICT round 5, next #1a).
 
     python tools/search_stats.py [frames]          -> one block per material on stderr/stdout
