@@ -1,7 +1,7 @@
 // k_quant_fast.h -- the speculative quantization pass of a FAST table set (quality 7, LAME's -f: noise_shaping == 0 and use_best_huffman == 0):
 // the reference's outer_loop returns right after bin_search_StepSize (Quantize.js:886-888) and iteration_finish_one has no best_huffman_divide.
 //
-// The general program (k_quant.h, k_quant_search.h: q_unit / q_outer_loop) computes exactly that for such a table set -- it reads the switches -- but it is one body for
+// The general program (k_quant_frame.h, k_quant_search.h: q_unit / q_outer_loop) computes exactly that for such a table set -- it reads the switches -- but it is one body for
 // every setting: the noise loop, the amplification, the Huffman region search and the count helpers are compiled into every kernel that holds it, and
 // they set its registers and its code size.  This file is the same granule-channel with nothing but what the fast mode runs, built from the q_*
 // functions of k_quant.h by calling them: load the lines, x^(3/4) and the energy test, what calc_xmin leaves behind that quantization reads
@@ -78,7 +78,7 @@ LHIP_DEV UnitOut q_unit_fast(const Tables& T, const PowBase& pb10, const Workspa
     u.bits = g.part2_3_length + g.part2_length;
     u.block_type = g.block_type;
     if (gr == 0) { LHIP_LANE_ONCE(i, 0, (SFBMAX) + 1) L.sf_gr0[ch][i] = (int8_t)L.sfb[i]; }
-    // ---- publish the record and the signed quantized spectrum: q_unit's statements (k_quant.h), a second copy to be changed with them (see there) ----
+    // ---- publish the record and the signed quantized spectrum: q_unit's statements (k_quant_frame.h), a second copy to be changed with them (see there) ----
     lane = lane_anew(lane);
     if (lane == 0) {
         out->part2_3_length = g.part2_3_length; out->part2_length = g.part2_length; out->big_values = g.big_values;

@@ -1,4 +1,4 @@
-// k_quant_framebits.h -- the size of a frame in bits and its padding bit.  The bit budget (k_quant.h) and the bit packer (k_bits.h) both
+// k_quant_framebits.h -- the size of a frame in bits and its padding bit.  The frame program (k_quant_frame.h) and the bit packer (k_bits.h) both
 // need them, and the packer needs nothing else of the search: this file depends on the definitions and the layout alone.
 #pragma once
 #include "lhip_defs.h"

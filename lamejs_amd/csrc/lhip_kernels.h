@@ -90,7 +90,7 @@ struct QArgs { Tables T; PowBase pb; Workspace W; const StreamDesc* SD; int chai
 // SKIP: the batch kernels exist in two forms -- with the search's dead last round of pairs skipped where the granule-channel's spectrum allows it (GI::tail0,
 // k_quant_count.h), and without any of that code: the host launches the second where the configuration's lowpass leaves lines above 512 in every long block (320 kbps),
 // which would only carry the first form's larger code (measured: + 1 % of such a step)
-template <int RESV, int SKIP> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_unused) {
+template <int SKIP> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_unused) {
     __shared__ QuantTabs Q;
     __shared__ QuantLds L[QWAVES];
     __shared__ TailShare TS;
@@ -101,7 +101,7 @@ template <int RESV, int SKIP> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_
     q_copy_tabs(A->T, Q, threadIdx.x, 64 * QWAVES);
     if (threadIdx.x == 0) TS.drawing = QWAVES;
     if (threadIdx.x < QWAVES) TS.offer[threadIdx.x].state = 0;
-    const bool tail_help_on = !RESV && A->T.channels_out == 2;       // a one-channel frame is one chain: nothing to offer
+    const bool tail_help_on = A->T.channels_out == 2;       // a one-channel frame is one chain: nothing to offer
     __syncthreads();
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #ifdef LHIP_PHASE_PROF
@@ -116,8 +116,7 @@ template <int RESV, int SKIP> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_
         if (fslot >= A->nfs) break;
         // the speculative pass (chain == 0): the frame program with the second channel of every granule on offer to the workgroup's idle waves
         // (k_quant_tail.h); with the reservoir the frames are a chain and this kernel is not launched (g_resv_stream)
-        if constexpr (!RESV) kb_quant_th<SKIP>(A->T, A->pb, A->W, A->SD, fslot, threadIdx.x & 63, L[wv], Q, hint, TS, wv);
-        else kb_quant<0, RESV, SKIP>(A->T, A->pb, A->W, A->SD, fslot, A->chain, threadIdx.x & 63, L[wv], Q, -1, nullptr, nullptr, nullptr);
+        kb_quant_th<SKIP>(A->T, A->pb, A->W, A->SD, fslot, threadIdx.x & 63, L[wv], Q, hint, TS, wv);
         hint[0] = __builtin_amdgcn_readfirstlane(hint[0]); hint[1] = __builtin_amdgcn_readfirstlane(hint[1]); hint[2] = __builtin_amdgcn_readfirstlane(hint[2]);
     }
     // the dispenser is empty: stay and take the second channels that this workgroup's waves still have ahead of them
@@ -135,7 +134,7 @@ template <int RESV, int SKIP> __global__ LHIP_QUANT_BOUNDS void g_quant(QArgs a_
 // Latency path for small stereo batches: one workgroup of two waves per frame, one wave per channel (kb_quant<1>).  A single
 // frame is one wave's serially dependent search; with fewer frames than SIMDs the chip is idle anyway, so the two channels
 // of a granule -- independent given the granule's bit budget -- run side by side.
-template <int RESV, int SKIP> __global__ __launch_bounds__(128, LHIP_QOCC) void g_quant_pair(QArgs a_unused) {
+template <int SKIP> __global__ __launch_bounds__(128, LHIP_QOCC) void g_quant_pair(QArgs a_unused) {
     __shared__ QuantTabs Q;
     __shared__ QuantLds L[2];
     __shared__ int mbox[4];
@@ -143,7 +142,7 @@ template <int RESV, int SKIP> __global__ __launch_bounds__(128, LHIP_QOCC) void 
     q_copy_tabs(A->T, Q, threadIdx.x, 128);
     __syncthreads();
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    kb_quant<1, RESV, SKIP>(A->T, A->pb, A->W, A->SD, blockIdx.x, A->chain, threadIdx.x & 63, L[wv], Q, wv, mbox);
+    kb_quant<1, 0, SKIP>(A->T, A->pb, A->W, A->SD, blockIdx.x, A->chain, threadIdx.x & 63, L[wv], Q, wv, mbox);
 }
 // Fast table sets (quality 7): the speculative pass as the bin search alone (k_quant_fast.h), persistent like g_quant.  PAIR == 1 (two channels): the waves
 // 2p, 2p + 1 of a workgroup are a pair -- wave 2p draws the pair's frame slots, each wave quantizes one channel; pairs never wait for each other.  PAIR == 0

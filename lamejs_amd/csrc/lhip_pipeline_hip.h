@@ -143,8 +143,8 @@ static bool run_pipeline(Context* ctx, BatchPlan& P) {
     { QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 0; qa.nfs = nfs; qa.ctr = 0;
       P.ql.workgroups = pair ? nfs : qgrid; P.ql.waves = pair ? 2 : QWAVES; P.ql.nfs = nfs; P.ql.kernel = pair ? QL_PAIR : QL_PERSISTENT; P.ql.pair = pair; P.ql.skip = ts.skip_tail;
       // (which form is a matter of speed only: the skip itself is decided per granule-channel from its spectrum)
-      if (pair) { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant_pair<0, 1>), nfs, 128, st, qa); else LAUNCHB(KT_QUANT, (g_quant_pair<0, 0>), nfs, 128, st, qa); }
-      else { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant<0, 1>), qgrid, 64 * QWAVES, st, qa); else LAUNCHB(KT_QUANT, (g_quant<0, 0>), qgrid, 64 * QWAVES, st, qa); } }
+      if (pair) { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant_pair<1>), nfs, 128, st, qa); else LAUNCHB(KT_QUANT, (g_quant_pair<0>), nfs, 128, st, qa); }
+      else { if (ts.skip_tail) LAUNCHB(KT_QUANT, (g_quant<1>), qgrid, 64 * QWAVES, st, qa); else LAUNCHB(KT_QUANT, (g_quant<0>), qgrid, 64 * QWAVES, st, qa); } }
     if (nfr > 0) {
         // validation of the seed chain + repair of the flagged frames, decided on the device (no host round trip in the pipeline)
         QArgs qa; qa.T = T; qa.pb = ts.pb10; qa.W = W; qa.SD = dSD; qa.chain = 1; qa.nfs = nfs; qa.ctr = 0;

@@ -330,7 +330,7 @@ static bool derive_index_tables(TableSet& ts, void* stream) {
             }
         }
     }
-    // psyA's partition energies as a systolic fold (k_psy.h): lane l owns the FFT lines 8 l .. 8 l + 7; per lane three words -- marks
+    // psyA's partition energies as a systolic fold (k_psy_a.h): lane l owns the FFT lines 8 l .. 8 l + 7; per lane three words -- marks
     // (bit k: line 8 l + k is the first of its partition, bit 8 + k: the last one, counting line 512 as part of the spectrum) and
     // the partition numbers of its eight lines, a byte each
     const size_t psyfold_at = extra.size();

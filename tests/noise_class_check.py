@@ -62,7 +62,7 @@ def check_div_by_f32(lib, n=600000, seed=11):
 
 
 def check_ma_index(lib, n=400000, seed=13):
-    """mask_add's table index ToInt32(log10(ratio) * 16) without the logarithm (k_psy.h ma_index16, v_log_f32 behind it on the device): wherever
+    """mask_add's table index ToInt32(log10(ratio) * 16) without the logarithm (k_psy_b.h ma_index16, v_log_f32 behind it on the device): wherever
     the shortcut answers it must be the logarithm's index -- random ratios over the range the psychoacoustic model produces and every step
     10^(k / 16) approached from both sides down to one ulp."""
     rng = np.random.default_rng(seed)

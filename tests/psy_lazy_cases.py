@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE shared by tests/test_psy_lazy_cpu.py and tests/test_psy_lazy_gpu.py: the short-block psychoacoustics computed only where
-somebody reads them (a "lazy" batch: lhip_batch.h plan_batch, k_psy.h psy_need_s / psy_need_f).
+somebody reads them (a "lazy" batch: lhip_batch.h plan_batch, k_psy_a.h psy_need_s / psy_need_f).
 
 The psy call in granule slot g leaves its thresholds in W.E[g] (lhip_debug_read(2): 122 entries per psy channel -- en.l 22, en.s 39, thm.l 22,
 thm.s 39); the quantization of slot g + 1 reads them, the short ones only when that granule is a short block.  By definition, per call:

@@ -75,7 +75,7 @@ def test_device_noise_class_shortcut(lib):
 
 
 def test_device_mask_add_index_shortcut(lib):
-    """mask_add's table index ToInt32(log10(ratio) * 16) from v_log_f32 with a guard band (k_psy.h ma_index16): wherever the shortcut
+    """mask_add's table index ToInt32(log10(ratio) * 16) from v_log_f32 with a guard band (k_psy_b.h ma_index16): wherever the shortcut
     answers on the device it is the index the f64 logarithm gives -- 0.6 M ratios incl. every step approached down to one ulp."""
     from noise_class_check import check_ma_index
     took, n = check_ma_index(lib)

@@ -308,7 +308,7 @@ def test_hostsim_division_by_reciprocal_is_the_division(sim):
 
 
 def test_hostsim_mask_add_index_shortcut(sim):
-    """mask_add's table index without the logarithm (k_psy.h ma_index16): the logarithm's index wherever it answers."""
+    """mask_add's table index without the logarithm (k_psy_b.h ma_index16): the logarithm's index wherever it answers."""
     from noise_class_check import check_ma_index
     took, n = check_ma_index(sim)
     assert took > 0.9 * n

@@ -19,7 +19,7 @@ lib = lamejs_amd.load_library(X + "/liblamejs_wavesim_exp.so")
 bad = fuzz_gpu.run(N, 555001, lib=lib, max_frames=40) + fuzz_gpu.run(N, 555002, lib=lib, max_frames=40, cfgs=fuzz_gpu.LSF_CFGS) + fuzz_gpu.run(N, 555003, lib=lib, max_frames=40, joint=True)
 sys.exit(1 if bad else 0)
 PY
-(cd $X && bash tools/isa_build.sh /tmp/isa/kg_$NAME.s | grep -E "g_quantILi0|g_fixup")
+(cd $X && bash tools/isa_build.sh /tmp/isa/kg_$NAME.s | grep -E "g_quantILi|g_fixup")
 mkdir -p $R/lamejs_amd/lib/variants
 ${HIPCC:-/opt/rocm/bin/hipcc} --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Wno-unused-value -fPIC -shared -x hip $X/lamejs_amd/csrc/lhip_api.cpp -o $R/lamejs_amd/lib/variants/liblamejs_hip_$NAME.so
 echo "variant library: lamejs_amd/lib/variants/liblamejs_hip_$NAME.so (A/B: gpurun -- 'bash tools/ab_libraries_gpu.sh')"

@@ -2,7 +2,7 @@
 # DEV TOOL (CPU): how often every source line of the quantization wave program runs per frame -- the 64-lane simulation built with --coverage, one
 # batch of the bench's headline material (stereo 128 kbps `sine`, 63 frames through the 8-wave workgroup with tail help), gcov counts divided by 64
 # lanes and by the frames.  Next to the static instruction counts of tools/isa_lines.py this gives the dynamic instruction budget of a frame
-# without a GPU (it reproduces the PMC count within a few per cent).   usage: tools/wavesim_linecounts.sh [file first_line last_line]  (k_quant.h or a k_quant_*.h file; default: the amplification helpers of k_quant_amp.h)
+# without a GPU (it reproduces the PMC count within a few per cent).   usage: tools/wavesim_linecounts.sh [file first_line last_line]  (a k_quant_*.h file; default: the amplification helpers of k_quant_amp.h)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 B=/tmp/wsim_cov; rm -rf $B; mkdir -p $B
