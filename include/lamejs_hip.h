@@ -373,6 +373,31 @@ int lhip_debug_ingest(int format, int channels, const void* bytes, size_t nsampl
  * scalefac[b + 1] ^= 1 (the band above alone), wanted.  c-h run only where lines exist (ix_in given, or the gain not refused).  max_noise is 0 where calc_noise did not form it (not wanted and
  * over_count > 0).  Returns 0 or < 0. */
 int lhip_debug_quant_probe(lhip_stream* s, const void* in, size_t n, void* out, int max_workgroups);
+/* Test hook.  lhip_debug_bits_probe: THE KERNEL g_bits_probe (in the simulation libraries: the same bodies) -- the bitstream formatter over n frames `in`, results to
+ * the n records `out`, with the tables of stream s (any option set: protect, header flags, joint, a downmix's one output channel).  The kernel calls the packers the
+ * library launches, kb_bits and kb_bits_mw, and restates nothing of them.  It reads and writes nothing of the stream's state.  Record k is frame k of a fresh
+ * stream: its padding bit comes from the stream's own rule (the slot lag a fresh stream starts with), its place in the output from the packer's closed form.
+ * form 0: kb_bits, one wave per workgroup; a wave takes frame after frame through one LDS image.  form 1: kb_bits_mw on GR * C waves of one workgroup, which
+ * pack the granule-channels side by side into wave 0's image and meet on two LDS counters, as the one-frame program's last phase does; each wave starts at the
+ * bit position the side records announce.  max_workgroups: 0 the default grid, 1 every record through one workgroup, k at most k workgroups (the simulations
+ * run at most 3).  GR = 2 for MPEG-1, 1 for MPEG-2 / 2.5; C = the stream's output channels.  Little-endian, natural alignment.
+ * Record in, GR * C * 1616 bytes:   GR * C side records in (granule, channel) order, then i16 l3[GR * C][576], the signed quantized lines.  A side record, 464
+ *   bytes, is the library's own (lhip_debug_read(4)), 116 i32: part2_3_length, part2_length, big_values, count1, global_gain, scalefac_compress, block_type,
+ *   table_select[3], subblock_gain[3], region0_count, region1_count, preflag, scalefac_scale, count1table_select, sfbmax, sfbdivide, 5 words the packer does
+ *   not read, scfsi (read from granule 1's records: bit i = band i), scalefac[39] (-1: a band shared through scfsi, granule 1 only; MPEG-2: the partitions' entries
+ *   in order, a negative one is written as 0), 50 words the packer does not read, mode_ext (read from the first record, joint stereo only).
+ * Record out, 1464 bytes:   u8 bytes[1448] (the frame, zero behind it) | i32 nbytes | i32 status (0; -1: no frame found where the packer could have placed it;
+ *   -2: bytes written behind the frame's end) | i64 offset, where in its stream's output the packer placed the frame (read off the output buffer: each record has
+ *   a zeroed window of its own there).
+ * Refused (< 0, lhip_last_error names the record, the granule-channel and the field) before anything is launched: null arguments, n = 0 or above 8192, a form
+ * other than 0 and 1, a bit reservoir stream, and any record with big_values odd or above 576; count1 outside big_values..576 or count1 - big_values not a
+ * multiple of 4; a table_select that names no table (4, above 31; 14 is written as 16); |l3| above the largest value of its region's table (15 + 2^linbits - 1
+ * with linbits, 0 under table 0) or above 8206; a non-zero line at or above count1; a line above 1 in the count1 region; region0_count above 15, region1_count
+ * above 7 (a normal block's: a start / stop block's counts are not transmitted) or their sum past the 22 long bands; sfbmax above 39; sfbdivide above sfbmax; scalefac_compress above 15 (MPEG-2: above 399, or outside 500..511
+ * with preflag); scfsi above 15; block_type, global_gain, subblock_gain, preflag, scalefac_scale, count1table_select or mode_ext outside their fields; a
+ * scalefactor that does not fit its slen (or -1 outside granule 1); part2_length + part2_3_length above 4095 or different from the bits the record will occupy
+ * (kb_bits_mw takes the announced value on trust); a frame whose side information and parts exceed the frame's bits.  Returns 0 or < 0. */
+int lhip_debug_bits_probe(lhip_stream* s, const void* in, size_t n, void* out, int form, int max_workgroups);
 
 /* Debug/test taps (tests only): copy intermediate results of the most recent batch to the host.
  * what: 0 xr [granule][ch][576] f32, 1 blocktype [granule][ch] i32, 2 E [granule][psy ch][122] f32 (psy ch = ch, or L R mid side in joint stereo; thresholds

@@ -126,11 +126,12 @@ ABI = {
     "lhip_debug_gain_histogram": (_int, [_ptr, _ptr]),
     "lhip_debug_gain_windows": (_int, [_int, _int, _ptr, _ptr, _size, _ptr, _ptr]),
     "lhip_debug_quant_probe": (_int, [_ptr, _ptr, _size, _ptr, _int]),
+    "lhip_debug_bits_probe": (_int, [_ptr, _ptr, _size, _ptr, _int, _int]),
     "lhip_last_error": (ctypes.c_char_p, []),
     "lhip_version": (ctypes.c_char_p, []),
 }
 
-TEST_HOOKS_OPTIONAL_IN_NAMED_LIBRARIES = frozenset({"lhip_debug_quant_probe"})      # see load_library
+TEST_HOOKS_OPTIONAL_IN_NAMED_LIBRARIES = frozenset({"lhip_debug_quant_probe", "lhip_debug_bits_probe"})      # see load_library
 
 _lib = None
 

@@ -465,19 +465,21 @@ LHIP_DEV void kb_bits(const Tables& T, const Workspace& W, const StreamDesc* SD,
 // records announce (8 sideinfo_len + the lengths of the granule-channels before it) into the ONE frame image wsh (wave 0's; put_bits is an atomic OR);
 // wave 0 also writes header, side info and the stuffing.  The packing waves meet twice (image cleared | packed | copied out) on the counters meet[0], meet[1]
 // (LDS, zero on entry) -- not at the workgroup's barrier: the other waves of the workgroup are busy saving the state and must not hold the packers up.
-LHIP_DEV void kb_bits_mw(const Tables& T, const Workspace& W, const StreamDesc* SD, int fslot, int lane, BitsLds& L, uint32_t* wsh, int part, int nparts, int* meet) {
+// PH: the pieces to run, bit 0 what precedes the first meeting point, bit 1 what lies between the two, bit 2 what follows the second.  The kernels run all of
+// them (kb_bits_mw); the one-lane simulation of the test hook lhip_debug_bits_probe, whose waves run one after the other and do not meet, goes piece by piece.
+template <int PH> LHIP_DEV void kb_bits_mw_t(const Tables& T, const Workspace& W, const StreamDesc* SD, int fslot, int lane, BitsLds& L, uint32_t* wsh, int part, int nparts, int* meet) {
     BitsFrame F;
     bool ok = bits_frame(T, W, SD, fslot, F);
     const int C = T.channels_out, NGC = T.mode_gr * C;
-    if (ok) {
+    if ((PH & 1) && ok) {
         // everything this wave will read from memory is fetched before the first barrier: the side records and its own granule-channel's spectrum
         const int nwords = (F.frame_bits + 31) >> 5;
         for (int i = part * LHIP_NL + lane; i < nwords + 1; i += nparts * LHIP_NL) wsh[i] = 0;
         stage_words((uint32_t*)L.side, (const uint32_t*)(W.side + (int64_t)F.fidx * 2 * C), NGC * (int)(sizeof(GrSide) / 4), lane);
         if (part < NGC) stage_words(L.q, (const uint32_t*)(W.l3 + (((int64_t)F.fidx * 2 + part / C) * C + part % C) * 576), 288, lane);
     }
-    wg_meet(meet, nparts, lane);
-    if (ok) {
+    if (PH == 7) wg_meet(meet, nparts, lane);
+    if ((PH & 2) && ok) {
         const GrSide* side = L.side;
         int pos = 8 * T.sideinfo_len, end = pos;
         for (int gc = 0; gc < NGC; gc++) { const int n = side[gc].part2_3_length + side[gc].part2_length; if (gc < part) pos += n; end += n; }
@@ -488,8 +490,11 @@ LHIP_DEV void kb_bits_mw(const Tables& T, const Workspace& W, const StreamDesc* 
         }
         if (part == 0 && lane == 0) bits_stuffing(T, wsh, end, F.frame_bits);
     }
-    wg_meet(meet + 1, nparts, lane);
-    if (ok) bits_copy_out(T, W, F, wsh, part * LHIP_NL + lane, nparts * LHIP_NL);
+    if (PH == 7) wg_meet(meet + 1, nparts, lane);
+    if ((PH & 4) && ok) bits_copy_out(T, W, F, wsh, part * LHIP_NL + lane, nparts * LHIP_NL);
+}
+LHIP_DEV void kb_bits_mw(const Tables& T, const Workspace& W, const StreamDesc* SD, int fslot, int lane, BitsLds& L, uint32_t* wsh, int part, int nparts, int* meet) {
+    kb_bits_mw_t<7>(T, W, SD, fslot, lane, L, wsh, part, nparts, meet);
 }
 
 }  // namespace lhip

@@ -19,6 +19,7 @@
 #include "k_quant_fast.h"      // the speculative pass of a fast table set (quality 7): the bin search alone
 #include "k_quant_probe.h"     // test hook: the search's pure functions over caller-supplied records (lhip_debug_quant_probe)
 #include "k_bits.h"
+#include "k_bits_probe.h"      // test hook: the bit packer over caller-supplied frames (lhip_debug_bits_probe)
 #include "k_crc.h"
 #include "k_ingest.h"
 #include "k_gain.h"
@@ -986,6 +987,199 @@ int lhip_debug_quant_probe(lhip_stream* s, const void* in, size_t n, void* out, 
     } else set_err("hipMalloc failed");
     rt::dfree(dIn); rt::dfree(dOut);
     return ok ? 0 : LHIP_ERR_INTERNAL;
+}
+// Test hook.  lhip_debug_bits_probe: the bit packer -- kb_bits (form 0) or kb_bits_mw (form 1), k_bits.h -- over n caller-supplied frames with the tables of stream s
+// (k_bits_probe.h: how the frames are laid out for it).  Every index and every width the packer forms from a record is checked here first, and so is what
+// kb_bits_mw takes on trust: that a granule-channel occupies the bits its side record announces.
+struct BitsProbeTabs { const int32_t *xlen, *linmax, *off, *hlen, *sfb_l, *sfb_s, *slen1, *slen2; };
+// bits of the pairs [a, b) under table t, or -1 with *why set
+static int bits_probe_region(const BitsProbeTabs& H, int t, int a, int b, const int16_t* q, const char** why) {
+    if (a >= b) return 0;
+    if (t < 0 || t > 31 || (t != 0 && H.off[t] < 0)) { *why = "table_select: no such table"; return -1; }
+    int bits = 0;
+    const int lin = t > 15 ? H.xlen[t] : 0, vmax = t == 0 ? 0 : t > 15 ? 15 + H.linmax[t] : H.xlen[t] - 1;
+    for (int i = a; i < b; i += 2) {
+        int x1 = q[i] < 0 ? -q[i] : q[i], x2 = q[i + 1] < 0 ? -q[i + 1] : q[i + 1];
+        if (x1 > vmax || x2 > vmax || x1 > IXMAX_VAL || x2 > IXMAX_VAL) { *why = "l3: a value above its table's largest (or above 8206)"; return -1; }
+        if (t == 0) continue;
+        if (t > 15) { if (x1 > 14) { bits += lin; x1 = 15; } if (x2 > 14) { bits += lin; x2 = 15; } }
+        bits += H.hlen[H.off[t] + x1 * (t > 15 ? 16 : H.xlen[t]) + x2];
+    }
+    return bits;
+}
+// the bits granule-channel gc of a frame will occupy, or -1 with *why set
+static int bits_probe_check_gc(const Tables& T, const BitsProbeTabs& H, const GrSide& G, const int16_t* q, int gr, const char** why) {
+    const int GR = T.mode_gr;
+    if (G.big_values < 0 || G.big_values > 576 || (G.big_values & 1)) { *why = "big_values odd or outside 0..576"; return -1; }
+    if (G.count1 < G.big_values || G.count1 > 576 || ((G.count1 - G.big_values) & 3)) { *why = "count1 outside big_values..576 or not whole quadruples"; return -1; }
+    if (G.block_type < 0 || G.block_type > 3) { *why = "block_type outside 0..3"; return -1; }
+    if (G.global_gain < 0 || G.global_gain > 255) { *why = "global_gain outside 0..255"; return -1; }
+    if ((G.preflag | 1) != 1 || (G.scalefac_scale | 1) != 1 || (G.count1table_select | 1) != 1) { *why = "preflag / scalefac_scale / count1table_select outside 0..1"; return -1; }
+    for (int w = 0; w < 3; w++) if (G.subblock_gain[w] < 0 || G.subblock_gain[w] > 7) { *why = "subblock_gain outside 0..7"; return -1; }
+    if (G.mode_ext < 0 || G.mode_ext > 3) { *why = "mode_ext outside 0..3"; return -1; }
+    if (G.sfbmax < 0 || G.sfbmax > SFBMAX) { *why = "sfbmax outside 0..39"; return -1; }
+    if (G.sfbdivide < 0 || G.sfbdivide > G.sfbmax) { *why = "sfbdivide outside 0..sfbmax"; return -1; }
+    if (G.scfsi < 0 || G.scfsi > 15) { *why = "scfsi outside 0..15"; return -1; }
+    const bool sh = G.block_type == SHORT_TYPE;
+    int part2 = 0;
+    if (GR == 2) {
+        if (G.scalefac_compress < 0 || G.scalefac_compress > 15) { *why = "scalefac_compress outside 0..15"; return -1; }
+        const int s1 = H.slen1[G.scalefac_compress], s2 = H.slen2[G.scalefac_compress];
+        for (int sfb = 0; sfb < G.sfbmax; sfb++) {
+            const int v = G.scalefac[sfb], n = sfb < G.sfbdivide ? s1 : s2;
+            if (v == -1 && gr == 1) continue;                 // a band shared through scfsi: no field
+            if (v < 0 || v >= (1 << n)) { *why = "scalefac: a value that does not fit its slen"; return -1; }
+            part2 += n;
+        }
+    } else {
+        const bool pre = G.preflag != 0;
+        if (pre ? (G.scalefac_compress < 500 || G.scalefac_compress > 511) : (G.scalefac_compress < 0 || G.scalefac_compress > 399)) { *why = "scalefac_compress outside 0..399 (preflag: 500..511)"; return -1; }
+        const int sc = G.scalefac_compress - (pre ? 500 : 0);
+        const int sl[4] = {pre ? sc / 3 : (sc >> 4) / 5, pre ? sc % 3 : (sc >> 4) % 5, pre ? 0 : (sc >> 2) & 3, pre ? 0 : sc & 3};
+        const int np[4] = {pre ? (sh ? 18 : 11) : (sh ? 9 : 6), pre ? (sh ? 18 : 10) : (sh ? 9 : 5), pre ? 0 : (sh ? 9 : 5), pre ? 0 : (sh ? 9 : 5)};
+        for (int p = 0, i = 0; p < 4; p++)
+            for (int k = 0; k < np[p]; k++, i++) {
+                if (G.scalefac[i] >= (1 << sl[p])) { *why = "scalefac: a value that does not fit its slen"; return -1; }
+                part2 += sl[p];
+            }
+    }
+    int part3 = 0, b;
+    if (sh) {
+        int r1 = 3 * H.sfb_s[3]; if (r1 > G.big_values) r1 = G.big_values;
+        const int ts[2] = {G.table_select[0] == 14 ? 16 : G.table_select[0], G.table_select[1] == 14 ? 16 : G.table_select[1]};
+        if ((b = bits_probe_region(H, ts[0], 0, r1, q, why)) < 0) return -1; part3 += b;
+        if ((b = bits_probe_region(H, ts[1], r1, G.big_values, q, why)) < 0) return -1; part3 += b;
+        for (int i = 0; i < 2; i++) if (ts[i] < 0 || ts[i] > 31 || ts[i] == 4) { *why = "table_select: no such table"; return -1; }      // (written to the side info whatever the regions hold)
+    } else {
+        // (a start / stop block's counts are not transmitted: 7 and 13 in the encoder's records; only the index is bounded there)
+        const bool norm = G.block_type == NORM_TYPE;
+        if (G.region0_count < 0 || G.region1_count < 0 || (norm && (G.region0_count > 15 || G.region1_count > 7)) || G.region0_count + G.region1_count + 2 > SBMAX_l) { *why = "region0_count / region1_count: an index past sfb_l"; return -1; }
+        int r1 = H.sfb_l[G.region0_count + 1], r2 = H.sfb_l[G.region0_count + G.region1_count + 2];
+        if (r1 > G.big_values) r1 = G.big_values;
+        if (r2 > G.big_values) r2 = G.big_values;
+        int ts[3];
+        for (int i = 0; i < 3; i++) { ts[i] = G.table_select[i] == 14 ? 16 : G.table_select[i]; if (ts[i] < 0 || ts[i] > 31 || ts[i] == 4) { *why = "table_select: no such table"; return -1; } }
+        if ((b = bits_probe_region(H, ts[0], 0, r1, q, why)) < 0) return -1; part3 += b;
+        if ((b = bits_probe_region(H, ts[1], r1, r2, q, why)) < 0) return -1; part3 += b;
+        if ((b = bits_probe_region(H, ts[2], r2, G.big_values, q, why)) < 0) return -1; part3 += b;
+    }
+    const int32_t* c1 = H.hlen + H.off[32 + G.count1table_select];
+    for (int i = G.big_values; i < G.count1; i += 4) {
+        int p = 0;
+        for (int k = 0; k < 4; k++) { const int v = q[i + k]; if (v < -1 || v > 1) { *why = "l3: a value above 1 in the count1 region"; return -1; } p = 2 * p + (v != 0); }
+        part3 += c1[p];
+    }
+    for (int i = G.count1; i < 576; i++) if (q[i] != 0) { *why = "l3: a non-zero value at or above count1"; return -1; }
+    if (G.part2_length < 0 || G.part2_3_length < 0 || G.part2_length + G.part2_3_length > 4095) { *why = "part2_length + part2_3_length outside 0..4095"; return -1; }
+    if (G.part2_length + G.part2_3_length != part2 + part3) { *why = "part2_length + part2_3_length is not what the record occupies"; return -1; }
+    return part2 + part3;
+}
+int lhip_debug_bits_probe(lhip_stream* s, const void* in, size_t n, void* out, int form, int max_workgroups) {
+    if (!s || s->magic != 0x4c484950) { set_err("bad stream handle"); return LHIP_ERR_BAD_HANDLE; }
+    if (!in || !out || n == 0 || n > (size_t)BITS_PROBE_MAX_RECORDS || max_workgroups < 0 || (form | 1) != 1) { set_err("lhip_debug_bits_probe: bad argument"); return LHIP_ERR_INTERNAL; }
+    const Tables& T = s->ts->T;
+    if (!T.disable_reservoir) { set_err("lhip_debug_bits_probe: a bit reservoir stream (its frames are not self-contained)"); return LHIP_ERR_INTERNAL; }
+    const uint8_t* blob = s->ts->blob.data();
+    BitsProbeTabs H;
+    {
+        const char* names[8] = {"ht_xlen", "ht_linmax", "ht_off", "ht_hlen", "sfb_l", "sfb_s", "slen1_tab", "slen2_tab"};
+        const int32_t** dst[8] = {&H.xlen, &H.linmax, &H.off, &H.hlen, &H.sfb_l, &H.sfb_s, &H.slen1, &H.slen2};
+        for (int i = 0; i < 8; i++) {
+            const lhtb_entry* e = find_entry(blob, names[i]);
+            if (!e || e->dtype != 1) { set_err(std::string("lhip_debug_bits_probe: tables blob without ") + names[i]); return LHIP_ERR_INTERNAL; }
+            *dst[i] = (const int32_t*)(blob + e->offset);
+        }
+    }
+    const int C = T.channels_out, GR = T.mode_gr, NGC = GR * C, nn = (int)n;
+    const size_t rec_bytes = (size_t)NGC * (sizeof(GrSide) + 576 * 2);
+    const int base = (int)s->ts->base_frame_bytes;
+    if (base + 1 > BITS_PROBE_FRAME_BYTES) { set_err("lhip_debug_bits_probe: frame larger than the record"); return LHIP_ERR_INTERNAL; }
+    // the workspace's arrays as the packer indexes them (two granule places per frame whatever GR), one StreamDesc and one output window per record
+    std::vector<GrSide> side((size_t)nn * 2 * C);
+    std::vector<int16_t> l3((size_t)nn * 2 * C * 576);
+    std::vector<StreamDesc> sd(nn);
+    std::vector<int32_t> fslot(nn), pads(nn);
+    std::vector<int64_t> win(nn);
+    memset((void*)side.data(), 0, side.size() * sizeof(GrSide));
+    memset((void*)sd.data(), 0, sd.size() * sizeof(StreamDesc));
+    int64_t out_bytes = 0;
+    int lag = T.frac_SpF;                                        // a fresh stream's (lhip_create)
+    for (int r = 0; r < nn; r++) {
+        const uint8_t* rec = (const uint8_t*)in + (size_t)r * rec_bytes;
+        memcpy((void*)&side[(size_t)r * 2 * C], rec, (size_t)NGC * sizeof(GrSide));         // (the caller's buffer need not be aligned)
+        memcpy(&l3[(size_t)r * 2 * C * 576], rec + (size_t)NGC * sizeof(GrSide), (size_t)NGC * 576 * 2);
+        pads[r] = host_next_padding(T, &lag);
+        int bits = 8 * T.sideinfo_len;
+        for (int gc = 0; gc < NGC; gc++) {
+            const char* why = nullptr;
+            const int b = bits_probe_check_gc(T, H, side[(size_t)r * 2 * C + gc], &l3[((size_t)r * 2 * C + gc) * 576], gc / C, &why);
+            if (b < 0) { set_err("lhip_debug_bits_probe: record " + std::to_string(r) + " granule-channel " + std::to_string(gc) + ": " + why); return LHIP_ERR_INTERNAL; }
+            bits += b;
+        }
+        if (bits > 8 * (base + pads[r])) { set_err("lhip_debug_bits_probe: record " + std::to_string(r) + ": the frame's parts exceed the frame's bits"); return LHIP_ERR_INTERNAL; }
+        // frame r of a stream starts r * base + (the padded frames before it) bytes in, and r frames hold at most r paddings: the window begins BITS_PROBE_SLACK
+        // bytes before the unpadded place and ends as many behind the fully padded one
+        win[r] = out_bytes;
+        out_bytes += (int64_t)base + 1 + r + 2 * BITS_PROBE_SLACK;
+        fslot[r] = r;
+        sd[r].nframes = nn; sd[r].fslot0 = -1; sd[r].gslot0 = -1; sd[r].out_slot0 = 0; sd[r].slot_lag = T.frac_SpF;
+        sd[r].out_off = win[r] + BITS_PROBE_SLACK - (int64_t)r * base;
+    }
+    Context* ctx = s->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!rt::set_device(ctx->device)) return LHIP_ERR_INTERNAL;
+    void* st = ctx->stream;
+    GrSide* dSide = (GrSide*)rt::dmalloc(side.size() * sizeof(GrSide));
+    int16_t* dL3 = (int16_t*)rt::dmalloc(l3.size() * 2);
+    StreamDesc* dSD = (StreamDesc*)rt::dmalloc(sd.size() * sizeof(StreamDesc));
+    int32_t* dFslot = (int32_t*)rt::dmalloc((size_t)nn * 4);
+    int32_t* dFB = (int32_t*)rt::dmalloc((size_t)nn * 4);
+    uint8_t* dOut = (uint8_t*)rt::dmalloc((size_t)out_bytes);
+    std::vector<uint8_t> hOut((size_t)out_bytes);
+    std::vector<int32_t> hFB(nn);
+    bool ok = dSide && dL3 && dSD && dFslot && dFB && dOut;
+    if (ok) {
+        ok = rt::h2d(dSide, side.data(), side.size() * sizeof(GrSide), st) && rt::h2d(dL3, l3.data(), l3.size() * 2, st) && rt::h2d(dSD, sd.data(), sd.size() * sizeof(StreamDesc), st) &&
+             rt::h2d(dFslot, fslot.data(), (size_t)nn * 4, st) && rt::dzero(dFB, (size_t)nn * 4, st) && rt::dzero(dOut, (size_t)out_bytes, st);
+        Workspace W; memset((void*)&W, 0, sizeof W);
+        W.nstreams = nn; W.nframes_total = nn; W.nfslots = nn;
+        W.fslot_stream = dFslot; W.side = dSide; W.l3 = dL3; W.out = dOut; W.frame_bytes = dFB;
+#ifndef LHIP_HOSTSIM
+        if (ok) {
+            BitsProbeArgs a; memset((void*)&a, 0, sizeof a);
+            a.T = T; a.W = W; a.SD = dSD; a.n = nn; a.form = form;
+            a.grid = max_workgroups > 0 ? (nn < max_workgroups ? nn : max_workgroups) : (nn < 1024 ? nn : 1024);
+            const std::string e = bits_probe_launch(rt::phys(ctx->device), a, st);
+            if (!e.empty()) { set_err("g_bits_probe: " + e); ok = false; }
+        }
+#else
+        if (ok) {
+            ok = rt::sync(st);
+            const int cap = max_workgroups > 0 && max_workgroups < PROBE_SIM_WAVES ? max_workgroups : PROBE_SIM_WAVES;
+            if (ok) bits_probe_sim_run(T, W, dSD, nn, nn < cap ? nn : cap, form);
+        }
+#endif
+        ok = ok && rt::d2h(hOut.data(), dOut, (size_t)out_bytes, st) && rt::d2h(hFB.data(), dFB, (size_t)nn * 4, st) && rt::sync(st);
+    } else set_err("hipMalloc failed");
+    rt::dfree(dSide); rt::dfree(dL3); rt::dfree(dSD); rt::dfree(dFslot); rt::dfree(dFB); rt::dfree(dOut);
+    if (!ok) return LHIP_ERR_INTERNAL;
+    // where did each frame land?  A frame begins with the sync byte 0xff, everything before it in its window is still zero
+    for (int r = 0; r < nn; r++) {
+        BitsProbeOut O; memset(&O, 0, sizeof O);
+        const int64_t wlen = (int64_t)base + 1 + r + 2 * BITS_PROBE_SLACK;
+        const uint8_t* w = hOut.data() + win[r];
+        int64_t first = 0;
+        while (first < wlen && w[first] == 0) first++;
+        O.nbytes = hFB[r];
+        O.offset = (int64_t)r * base - BITS_PROBE_SLACK + first;
+        if (O.nbytes < 0 || O.nbytes > BITS_PROBE_FRAME_BYTES || first + O.nbytes > wlen) O.status = -1;
+        else {
+            memcpy(O.bytes, w + first, (size_t)O.nbytes);
+            for (int64_t i = first + O.nbytes; i < wlen; i++) if (w[i] != 0) O.status = -2;       // bytes written behind the frame
+        }
+        memcpy((uint8_t*)out + (size_t)r * sizeof O, &O, sizeof O);
+    }
+    return 0;
 }
 int lhip_debug_info_toc(const int64_t* frames, size_t ncalls, int kbps, uint8_t* toc) {
     if ((!frames && ncalls) || !toc || kbps <= 0) { set_err("lhip_debug_info_toc: bad argument"); return LHIP_ERR_INTERNAL; }

@@ -440,29 +440,42 @@ static const bool g_trace = []() { const char* e = getenv("LAMEJS_HIP_TRACE"); r
 // lhip_create: the quantization kernels' tables gathered once into an HBM image (q_copy_tabs)
 __global__ __launch_bounds__(256) void g_build_qtabs(Tables T, QuantTabs* img) { q_load_tabs(T, *img, threadIdx.x, 256); }
 
-// Test hook (lhip_debug_quant_probe): the kernel g_quant_probe is compiled apart, from lhip_probe.cpp (which says why) into the code object lhip_quant_probe.co
-// beside this library; it is loaded per device on first use and launched through the module interface.  Returns "" or what went wrong; a library without the
-// file beside it (the profiling and experiment builds of tools/) has no probe, and says so.
-static std::string probe_launch(int phys_device, const ProbeArgs& a, void* stream) {
+// Test hooks (lhip_debug_quant_probe, lhip_debug_bits_probe): the kernels g_quant_probe and g_bits_probe are compiled apart, from lhip_probe.cpp (which says why)
+// into the code object lhip_quant_probe.co beside this library; it is loaded per device on first use and launched through the module interface.  Returns "" or
+// what went wrong; a library without the file beside it (the profiling and experiment builds of tools/) has no probe, and says so.
+static std::string probe_launch_kernel(int phys_device, const char* kernel, void* arg, int grid, int block, void* stream) {
     static std::mutex mu;
-    static std::map<int, hipFunction_t> loaded;
+    static std::map<int, hipModule_t> loaded;
+    static std::map<std::pair<int, std::string>, hipFunction_t> fns;
     std::lock_guard<std::mutex> lk(mu);
-    auto it = loaded.find(phys_device);
-    if (it == loaded.end()) {
+    auto fit = fns.find({phys_device, kernel});
+    if (fit == fns.end()) {
         Dl_info di;
         if (!dladdr((const void*)&lhip_version, &di) || !di.dli_fname) return "cannot find the library's own path";
         std::string path(di.dli_fname);
         const size_t cut = path.rfind('/');
         path = (cut == std::string::npos ? std::string() : path.substr(0, cut + 1)) + "lhip_quant_probe.co";
-        hipModule_t mod = nullptr; hipFunction_t fn = nullptr;
-        hipError_t e = hipModuleLoad(&mod, path.c_str());
-        if (e != hipSuccess) return path + ": " + hipGetErrorString(e);
-        e = hipModuleGetFunction(&fn, mod, "g_quant_probe");
-        if (e != hipSuccess) { (void)hipModuleUnload(mod); return path + ": g_quant_probe: " + hipGetErrorString(e); }
-        it = loaded.emplace(phys_device, fn).first;
+        auto it = loaded.find(phys_device);
+        if (it == loaded.end()) {
+            hipModule_t mod = nullptr;
+            const hipError_t e = hipModuleLoad(&mod, path.c_str());
+            if (e != hipSuccess) return path + ": " + hipGetErrorString(e);
+            it = loaded.emplace(phys_device, mod).first;
+        }
+        hipFunction_t fn = nullptr;
+        const hipError_t e = hipModuleGetFunction(&fn, it->second, kernel);
+        if (e != hipSuccess) return path + ": " + kernel + ": " + hipGetErrorString(e);
+        fit = fns.emplace(std::make_pair(phys_device, std::string(kernel)), fn).first;
     }
-    ProbeArgs arg = a;
-    void* params[] = {&arg};
-    const hipError_t e = hipModuleLaunchKernel(it->second, (unsigned)a.grid, 1, 1, 64, 1, 1, 0, (hipStream_t)stream, params, nullptr);
+    void* params[] = {arg};
+    const hipError_t e = hipModuleLaunchKernel(fit->second, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, 0, (hipStream_t)stream, params, nullptr);
     return e != hipSuccess ? std::string(hipGetErrorString(e)) : std::string();
+}
+static std::string probe_launch(int phys_device, const ProbeArgs& a, void* stream) {
+    ProbeArgs arg = a;
+    return probe_launch_kernel(phys_device, "g_quant_probe", &arg, a.grid, 64, stream);
+}
+static std::string bits_probe_launch(int phys_device, const BitsProbeArgs& a, void* stream) {
+    BitsProbeArgs arg = a;
+    return probe_launch_kernel(phys_device, "g_bits_probe", &arg, a.grid, a.form == 0 ? 64 : 64 * a.T.mode_gr * a.T.channels_out, stream);
 }

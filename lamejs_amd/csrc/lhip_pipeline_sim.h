@@ -33,6 +33,25 @@ static void quant_probe_sim_run(const Tables& T, const PowBase& pb, const ProbeI
     for (int b = 0; b < grid; b++)
         for (int r = b; r < n; r += grid) WAVE_RUN(kb_quant_probe(T, pb, in, out, r, lane_, LP[b], QT));
 }
+// g_bits_probe (lhip_debug_bits_probe; k_bits_probe.h): `grid` workgroups, each with LDS of its own that serves its frames one after the other.  form 0: kb_bits on one
+// wave.  form 1: kb_bits_mw on GR * C waves -- a real workgroup in the wave simulation; the one-lane simulation, whose waves run one after the other, goes through
+// kb_bits_mw's pieces (kb_bits_mw_t) (image cleared and inputs fetched | packed | copied out) wave by wave, which is what the two meeting points order.
+static void bits_probe_sim_run(const Tables& T, const Workspace& W, const StreamDesc* SD, int n, int grid, int form) {
+    static thread_local BitsLds LB[PROBE_SIM_WAVES][4];
+    const int np = T.mode_gr * T.channels_out;
+    for (int b = 0; b < grid; b++)
+        for (int r = b; r < n; r += grid) {
+            if (form == 0) { WAVE_RUN(kb_bits(T, W, SD, r, lane_, LB[b][0])); continue; }
+#ifdef LHIP_WAVESIM
+            int meet[2] = {0, 0};
+            wsim::run_block(np, [&](int wave_, int lane_) { kb_bits_mw(T, W, SD, r, lane_, LB[b][wave_], LB[b][0].w, wave_, np, meet); });
+#else
+            for (int part = 0; part < np; part++) kb_bits_mw_t<1>(T, W, SD, r, 0, LB[b][part], LB[b][0].w, part, np, nullptr);
+            for (int part = 0; part < np; part++) kb_bits_mw_t<2>(T, W, SD, r, 0, LB[b][part], LB[b][0].w, part, np, nullptr);
+            for (int part = 0; part < np; part++) kb_bits_mw_t<4>(T, W, SD, r, 0, LB[b][part], LB[b][0].w, part, np, nullptr);
+#endif
+        }
+}
 static inline bool g_kt_on_() { return false; }
 static bool collect_kernel_times(void*) { return true; }
 static bool collect_repair_stats(Context*, BatchPlan&, bool, const int32_t*) { return true; }      // (run_pipeline counted them itself)

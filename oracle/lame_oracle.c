@@ -369,10 +369,103 @@ static int lo_format_frame(lo_enc* e, uint8_t* out, int* main_bits) {
     if (main_bits) { *main_bits = w.bitpos - 8 * c->sideinfo_len; return 0; }
     lo_drain(c, &w, e->resvDrain_post);
     if (w.bitpos != frame_bits) {
+        if (e->probe) return -1;
         fprintf(stderr, "lame_oracle: frame %ld wrote %d bits, expected %d\n", e->frame_num, w.bitpos, frame_bits);
         abort();
     }
     return frame_bits / 8;
+}
+
+/* tap: the side state lo_format_frame is about to read (lo_tap's s_ fields) */
+static void lo_tap_side(lo_enc* e) {
+    lo_tap* t = e->tap;
+    int gr, ch, i;
+    t->s_padding = e->padding;
+    for (ch = 0; ch < 2; ch++) { t->s_scfsi[ch] = 0; for (i = 0; i < 4; i++) t->s_scfsi[ch] |= (e->scfsi[ch][i] ? 1 : 0) << i; }
+    for (gr = 0; gr < e->c.mode_gr; gr++)
+        for (ch = 0; ch < e->c.channels_out; ch++) {
+            const lo_gr* gi = &e->tt[gr][ch];
+            t->s_big_values[gr][ch] = gi->big_values; t->s_count1[gr][ch] = gi->count1;
+            for (i = 0; i < 3; i++) { t->s_table_select[gr][ch][i] = gi->table_select[i]; t->s_subblock_gain[gr][ch][i] = gi->subblock_gain[i]; }
+            t->s_region0_count[gr][ch] = gi->region0_count; t->s_region1_count[gr][ch] = gi->region1_count;
+            t->s_scalefac_compress[gr][ch] = gi->scalefac_compress; t->s_count1table_select[gr][ch] = gi->count1table_select;
+            t->s_sfbmax[gr][ch] = gi->sfbmax; t->s_sfbdivide[gr][ch] = gi->sfbdivide;
+            for (i = 0; i < SFBMAX; i++) t->s_scalefac[gr][ch][i] = gi->scalefac[i];
+            t->s_preflag[gr][ch] = gi->preflag; t->s_scalefac_scale[gr][ch] = gi->scalefac_scale; t->s_block_type[gr][ch] = gi->block_type;
+            t->s_global_gain[gr][ch] = gi->global_gain; t->s_part2_3_length[gr][ch] = gi->part2_3_length; t->s_part2_length[gr][ch] = gi->part2_length;
+            for (i = 0; i < 576; i++) t->s_l3[gr][ch][i] = (int16_t)(D(gi->xr[i]) < 0 ? -gi->l3_enc[i] : gi->l3_enc[i]);
+        }
+}
+
+/* ------------------------------------------------------------------ */
+/* the bitstream probe (tests/bits_probe_cases.py)                      */
+/* ------------------------------------------------------------------ */
+/* The library's side record (struct GrSide, lamejs_amd/csrc/lhip_defs.h): 116 int32 */
+typedef struct {
+    int32_t part2_3_length, part2_length, big_values, count1, global_gain, scalefac_compress, block_type, table_select[3], subblock_gain[3], region0_count,
+        region1_count, preflag, scalefac_scale, count1table_select, sfbmax, sfbdivide, unread_[5], scfsi, scalefac[SFBMAX], unread2_[50], mode_ext;
+} lo_bits_side;
+typedef struct { uint8_t bytes[1448]; int32_t nbytes, status; int64_t offset; } lo_bits_out;
+_Static_assert(sizeof(lo_bits_side) == 464 && sizeof(lo_bits_out) == 1464, "bits probe record layouts");
+
+int lo_bits_probe(lo_enc* e, const void* in, size_t n, void* out) {
+    const lo_cfg* c = &e->c;
+    const int C = c->channels_out, GR = c->mode_gr, NGC = GR * C;
+    const size_t rec = (size_t)NGC * (sizeof(lo_bits_side) + 576 * 2);
+    lo_enc* p;
+    uint8_t* tmp;
+    size_t r;
+    int64_t offset = 0;
+    if (!c->disable_reservoir) return -1;
+    p = (lo_enc*)calloc(1, sizeof(lo_enc));
+    tmp = (uint8_t*)malloc(1 << 16);
+    p->c = *c; p->probe = 1;
+    p->slot_lag = c->frac_SpF;                           /* a fresh stream's (lo_create) */
+    for (r = 0; r < n; r++) {
+        const uint8_t* I = (const uint8_t*)in + r * rec;
+        lo_bits_out O;
+        int gc, i, used = 8 * c->sideinfo_len, nb;
+        memset(&O, 0, sizeof O);
+        memset(tmp, 0, 1 << 16);
+        p->padding = 0;
+        if ((p->slot_lag -= c->frac_SpF) < 0) { p->slot_lag += c->out_samplerate; p->padding = 1; }
+        p->frame_num = (long)r;
+        for (gc = 0; gc < NGC; gc++) {
+            lo_bits_side S;
+            int16_t q[576];
+            lo_gr* gi = &p->tt[gc / C][gc % C];
+            memcpy(&S, I + (size_t)gc * sizeof S, sizeof S);
+            memcpy(q, I + (size_t)NGC * sizeof S + (size_t)gc * 576 * 2, sizeof q);
+            memset(gi, 0, sizeof *gi);
+            for (i = 0; i < 576; i++) { gi->l3_enc[i] = q[i] < 0 ? -q[i] : q[i]; gi->xr[i] = q[i] < 0 ? -1.f : 1.f; }
+            for (i = 0; i < SFBMAX; i++) gi->scalefac[i] = S.scalefac[i];
+            gi->part2_3_length = S.part2_3_length; gi->part2_length = S.part2_length; gi->big_values = S.big_values; gi->count1 = S.count1;
+            gi->global_gain = S.global_gain; gi->scalefac_compress = S.scalefac_compress; gi->block_type = S.block_type; gi->mixed_block_flag = 0;
+            for (i = 0; i < 3; i++) { gi->table_select[i] = S.table_select[i]; gi->subblock_gain[i] = S.subblock_gain[i]; }
+            gi->region0_count = S.region0_count; gi->region1_count = S.region1_count; gi->preflag = S.preflag; gi->scalefac_scale = S.scalefac_scale;
+            gi->count1table_select = S.count1table_select; gi->sfbmax = S.sfbmax; gi->sfbdivide = S.sfbdivide;
+            if (GR == 2 && gc / C == 1) for (i = 0; i < 4; i++) p->scfsi[gc % C][i] = (S.scfsi >> i) & 1;
+            if (gc == 0) p->mode_ext = c->mode == 1 ? S.mode_ext : 0;
+            if (GR == 1) {
+                /* what a decoder derives from scalefac_compress (ISO 13818-3 2.4.3.2; no intensity stereo): below 400 four widths over partition table 0,
+                 * 500 .. 511 (preflag) two widths over table 2; the row is the block type's */
+                const int sc = S.scalefac_compress;
+                if (sc < 400) { gi->slen[0] = (sc >> 4) / 5; gi->slen[1] = (sc >> 4) % 5; gi->slen[2] = (sc & 15) >> 2; gi->slen[3] = sc & 3; gi->sfb_part_tab = 0; }
+                else { gi->slen[0] = (sc - 500) / 3; gi->slen[1] = (sc - 500) % 3; gi->slen[2] = 0; gi->slen[3] = 0; gi->sfb_part_tab = 2; }
+                gi->sfb_part_row = S.block_type == SHORT_TYPE ? 1 : 0;
+            }
+            used += S.part2_3_length + S.part2_length;
+        }
+        p->resvDrain_post = lo_frame_bits(p) - used;      /* ResvFrameEnd: everything left is drained into the frame's ancillary data */
+        nb = lo_format_frame(p, tmp, NULL);
+        O.offset = offset;
+        offset += lo_frame_bits(p) / 8;
+        if (nb < 0 || nb > (int)sizeof O.bytes) O.status = -1;
+        else { O.nbytes = nb; memcpy(O.bytes, tmp, (size_t)nb); }
+        memcpy((uint8_t*)out + r * sizeof O, &O, sizeof O);
+    }
+    free(tmp); free(p);
+    return 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -571,6 +664,7 @@ static int lo_encode_frame(lo_enc* e, uint8_t* out) {
         return n;
     }
     lo_iteration_loop(e, (e->mode_ext == 2) ? masking_MS : masking, ms_ener_ratio);
+    if (e->tap) lo_tap_side(e);
     n = lo_format_frame(e, out, NULL);
     e->frame_num++;
     return n;

@@ -23,6 +23,11 @@ const void* lo_get_tap(const lo_enc* e);
 size_t lo_tap_size(void);
 /* the quantization probe (lo_quant.c): n records of 4144 bytes in, n of 6352 bytes out, with e's tables; e's stream state is left as it was */
 void lo_quant_probe(lo_enc* e, const void* in, size_t n, void* out);
+/* the bitstream probe (lame_oracle.c): n frames in (mode_gr * channels side records of 464 bytes, then as many signed int16 spectra of 576 lines: the layout of the
+ * library's lhip_debug_bits_probe), n records of 1464 bytes out (frame bytes[1448], int32 nbytes, int32 status, int64 offset); record k is formatted as frame k of
+ * a fresh stream by lo_format_frame.  status -1: the record does not fill its frame exactly (where the encoder's path aborts).  No bit reservoir; e's stream
+ * state is left as it was.  Returns 0, or -1 for a reservoir configuration. */
+int lo_bits_probe(lo_enc* e, const void* in, size_t n, void* out);
 #ifdef __cplusplus
 }
 #endif

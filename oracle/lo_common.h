@@ -135,6 +135,7 @@ typedef struct lo_enc {
     float nb_1[4][CBANDS], nb_2[4][CBANDS];     /* long-block pre-echo control (PsyModel.js:1300-1318): live once pcfact != 0 */
     struct lo_stream* bs;                       /* the continuous bitstream writer (headers are inserted where their frame starts) */
     int slot_lag, padding;
+    int probe;                                  /* lo_bits_probe: lo_format_frame reports a frame that does not fill its bits instead of aborting */
     /* optional per-frame taps for differential debugging (tests only) */
     struct lo_tap* tap;
 } lo_enc;
@@ -153,6 +154,11 @@ typedef struct lo_tap {
     int active[2][2];              /* init_xrpow found energy; 0: the fields below are zero */
     int scalefac[2][2][SFBMAX], scalefac_scale[2][2], preflag[2][2], subblock_gain[2][2][3];
     int l3_enc[2][2][576];         /* magnitudes, quantizer line order */
+    /* the complete side state the formatter reads (no bit reservoir), as it stands when lo_format_frame is called: what tests/bits_probe_cases.py harvests */
+    int s_big_values[2][2], s_count1[2][2], s_table_select[2][2][3], s_region0_count[2][2], s_region1_count[2][2], s_scalefac_compress[2][2],
+        s_count1table_select[2][2], s_sfbmax[2][2], s_sfbdivide[2][2], s_scfsi[2], s_scalefac[2][2][SFBMAX], s_preflag[2][2], s_scalefac_scale[2][2],
+        s_subblock_gain[2][2][3], s_block_type[2][2], s_global_gain[2][2], s_part2_3_length[2][2], s_part2_length[2][2], s_padding, s_pad_;
+    int16_t s_l3[2][2][576];       /* signed: l3_enc with xr's sign */
 } lo_tap;
 
 #endif

@@ -39,7 +39,8 @@ def _load():
         vp, sz = ctypes.c_void_p, ctypes.c_size_t
         for name, restype, argtypes in (("lo_create", vp, [vp, sz]), ("lo_destroy", None, [vp]), ("lo_encode", ctypes.c_long, [vp, vp, vp, sz, vp, sz]),
                                         ("lo_flush", ctypes.c_long, [vp, vp, sz]), ("lo_enable_tap", None, [vp]), ("lo_get_tap", vp, [vp]),
-                                        ("lo_tap_size", sz, []), ("lo_math", None, [ctypes.c_int, vp, vp, sz]), ("lo_quant_probe", None, [vp, vp, sz, vp])):
+                                        ("lo_tap_size", sz, []), ("lo_math", None, [ctypes.c_int, vp, vp, sz]), ("lo_quant_probe", None, [vp, vp, sz, vp]),
+                                        ("lo_bits_probe", ctypes.c_int, [vp, vp, sz, vp])):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -88,6 +89,14 @@ class OracleStream:
         rec = np.ascontiguousarray(records)
         out = np.zeros(len(rec), dtype=out_dtype)
         self._lib.lo_quant_probe(self._h, rec.ctypes.data, len(rec), out.ctypes.data)
+        return out
+
+    def bits_probe(self, records, out_dtype):
+        """lo_bits_probe over an array of frame records (tests/bits_probe_cases.py: rec_in) -> array of ``out_dtype`` (REC_OUT)."""
+        rec = np.ascontiguousarray(records)
+        out = np.zeros(len(rec), dtype=out_dtype)
+        if self._lib.lo_bits_probe(self._h, rec.ctypes.data, len(rec), out.ctypes.data) != 0:
+            raise RuntimeError("lo_bits_probe refused the configuration")
         return out
 
     def close(self):

@@ -19,7 +19,14 @@ TAP = np.dtype([("xr", "<f4", (2, 2, 576)), ("block_type", "<i4", (2, 2)), ("rat
                 ("ms_ener_ratio", "<f8", (2,)),
                 # the search's final state (after outer_loop): what tests/quant_probe_cases.py feeds back into calc_noise
                 ("active", "<i4", (2, 2)), ("scalefac", "<i4", (2, 2, SFBMAX)), ("scalefac_scale", "<i4", (2, 2)), ("preflag", "<i4", (2, 2)),
-                ("subblock_gain", "<i4", (2, 2, 3)), ("l3_enc", "<i4", (2, 2, 576))], align=True)
+                ("subblock_gain", "<i4", (2, 2, 3)), ("l3_enc", "<i4", (2, 2, 576)),
+                # the complete side state the formatter reads, as it stands when the frame is formatted (no bit reservoir): what tests/bits_probe_cases.py harvests
+                ("s_big_values", "<i4", (2, 2)), ("s_count1", "<i4", (2, 2)), ("s_table_select", "<i4", (2, 2, 3)), ("s_region0_count", "<i4", (2, 2)),
+                ("s_region1_count", "<i4", (2, 2)), ("s_scalefac_compress", "<i4", (2, 2)), ("s_count1table_select", "<i4", (2, 2)), ("s_sfbmax", "<i4", (2, 2)),
+                ("s_sfbdivide", "<i4", (2, 2)), ("s_scfsi", "<i4", (2,)), ("s_scalefac", "<i4", (2, 2, SFBMAX)), ("s_preflag", "<i4", (2, 2)),
+                ("s_scalefac_scale", "<i4", (2, 2)), ("s_subblock_gain", "<i4", (2, 2, 3)), ("s_block_type", "<i4", (2, 2)), ("s_global_gain", "<i4", (2, 2)),
+                ("s_part2_3_length", "<i4", (2, 2)), ("s_part2_length", "<i4", (2, 2)), ("s_padding", "<i4"), ("s_pad_", "<i4"),
+                ("s_l3", "<i2", (2, 2, 576))], align=True)
 
 # struct GrSide (lamejs_amd/csrc/lhip_defs.h), 32-bit fields in declaration order
 _GRSIDE_FIELDS = (["part2_3_length", "part2_length", "big_values", "count1", "global_gain", "scalefac_compress", "block_type"] +
